@@ -14,7 +14,16 @@ produces block b+1 while the stereo and RDS chains consume block b, ordered by e
 the ThreadSafeQueue protocol (include/threadsafequeue.h:24-74). With N > 1 each block-step's stereo
 audio and RDS bits are gathered to rank 0 over RCCL (xGMI) on a fourth, non-blocking stream.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--channels C] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--channels C] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, and
+the roofline / pll figures read from the timed steps' own stamps). --dump-outputs DIR also writes the
+outputs of the last timed step (mono, stereo, rds_clean, rds_bits, rds_nbits; one row per channel,
+float32) as DIR/<name>.npy; the input is seeded, so two builds can be compared array for array.
+The set-up generates min(W + K, INPUT_RING = 160) input blocks; a longer run reads them round (block b
+is block b % 160), so its set-up time and memory do not grow with K.
+--full adds, after the timed steps: the bit-for-bit check of 8 channels against the oracle (`verified`),
+the CPU baselines, the isolated front-end and HBM copy timings and the queue-plumbed receiver
+(--no-cpu-baseline / --no-isolated leave parts of those out).
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts N ranks itself
 (torch.distributed.run, 127.0.0.1) and exits with their status; the driver may also launch it
 under torch.distributed.run directly.
@@ -40,6 +49,11 @@ HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-l
 FP32_VECTOR_PEAK_TF = 157.3     # MI355X FP32 vector (packed) peak, TFLOP/s
 METRIC = "IQ MSamples/s/node (mono+stereo+RDS), 1/2/4/8 GPU; HBM GB/s %peak"
 VERIFY_CHANNELS = 8             # channels of rank 0 whose outputs are checked after the timed run
+DUMP_MAX_BYTES = 60 << 20       # --dump-outputs: all arrays together (float32) stay below 64 MB
+# Distinct input blocks resident in HBM. A run of more blocks (warm-up + steps) reads them round, block b
+# being block b % INPUT_RING, so that its set-up time (~17 ms to generate a block of 1024 channels) and
+# its memory (150 MB per block) do not grow with --steps. The default run (140 blocks) does not wrap.
+INPUT_RING = 160
 
 
 def _load_pkg():
@@ -183,8 +197,9 @@ class GpuStepper:
         # 2312-2325 MHz, 0.7057-0.7076 -> 0.7032-0.7063 ms per step over 3 interleaved pairs at the
         # driver's 20/5, profiles/r06/input_last_ab.txt); SDR_BENCH_INPUT_LAST=0: first, as before
         self.input_last = os.environ.get("SDR_BENCH_INPUT_LAST", "1") == "1"
+        self.ring = min(nblocks, INPUT_RING)      # input blocks generated; block b reads b % ring
         if not self.input_last:
-            self.iq = make_input(torch, nch, nblocks, first_channel=first, device=dev)
+            self.iq = make_input(torch, nch, self.ring, first_channel=first, device=dev)
         fast = args.numerics == "fast"
         self.fast = fast
         self.pipe = pkg.Pipeline(nch, mode=0, rds_on=True, device=local,
@@ -268,7 +283,7 @@ class GpuStepper:
         self.pre_done, self.post_done = [tev() for _ in range(nblocks)], [tev() for _ in range(nblocks)]
         self.post_dsp_done = [ev() for _ in range(nblocks)]   # block b's post DSP (before its captures)
         if self.input_last:
-            self.iq = make_input(torch, nch, nblocks, first_channel=first, device=dev)
+            self.iq = make_input(torch, nch, self.ring, first_channel=first, device=dev)
         # the front end of block b also waits for block b-2's whole post stream work (the RDS chain
         # after its mixer, the output copies and captures included), not only for the library's own
         # parity release (its readers' first kernels): the front end then runs beside the PLL alone
@@ -365,10 +380,10 @@ class GpuStepper:
         if first and self.persist and self.fill_parts > 1:
             # the pipeline fill: the phase's first block in sample ranges, each published to the
             # persistent PLL as soon as its front end and pre-PLL FIRs are done
-            pipe.frontend_pre_parts(self.iq[b], self.fill_parts, stream=s_fe)
+            pipe.frontend_pre_parts(self.iq[b % self.ring], self.fill_parts, stream=s_fe)
             self.parts_block = b
         else:
-            pipe.frontend(self.iq[b], stream=s_fe)            # rffrontend.cpp:58-71
+            pipe.frontend(self.iq[b % self.ring], stream=s_fe)            # rffrontend.cpp:58-71
             self.fe_end[b].record(s_fe)
             pipe.pre(stream=s_fe)                             # stereo.cpp:74, :80 + rds.cpp:105-116
             if self.persist:                                  # stereo.cpp:77 + rds.cpp:119
@@ -644,7 +659,7 @@ class GpuStepper:
             p2.frontend_timing(reps)
             e0.record(s2)
             for b in range(reps):
-                p2.frontend(self.iq[b % self.nblocks], stream=s2)
+                p2.frontend(self.iq[b % self.ring], stream=s2)
             e1.record(s2)
             torch.cuda.synchronize(self.dev)
             ms_calls = e0.elapsed_time(e1) / reps
@@ -698,11 +713,34 @@ class GpuStepper:
     def captured(self) -> dict:
         """Host copies of the inputs and captured outputs of the checked channels."""
         sel = self.vsel.cpu().numpy()
-        iq = self.iq[:, self.vsel].cpu().numpy()            # [nblocks][nv][2*block_iq]
+        iq = self.iq[:, self.vsel].cpu().numpy()[np.arange(self.nblocks) % self.ring]   # [nblocks][nv][2*block_iq]
         lr, bits = self.cap_lr.cpu().numpy(), self.cap_bits.cpu().numpy()
         return {"channels": [int(c) for c in sel], "first_channel": self.first, "iq": iq,
                 "mono": self.cap_mono.cpu().numpy(), "lr": lr, "bits": bits, "nbits": self.cap_nbits.cpu().numpy(),
                 "digest": _digest(lr, bits)}
+
+    def last_outputs(self, max_bytes: int = DUMP_MAX_BYTES) -> dict:
+        """--dump-outputs: what the last timed step handed to a caller of the pipeline, as float32
+        host arrays with one row per channel: mono and stereo PCM, rds_clean, the RDS bits (-1 past
+        the nbits[channel] bits the row holds: the buffer is not written there) and nbits. Past
+        max_bytes in all, the rows of a fixed, seeded choice of channels (`channels`)."""
+        torch = self.torch
+        b = self.nblocks - 1
+        nbits = self.pipe.nbits
+        col = torch.arange(self.pkg.SDR_MAX_BITS, device=self.dev)
+        bits = torch.where(col[None, :] < nbits[:, None], self.bits[b % 2].to(torch.int32), -1)
+        outs = {"mono": self.mono, "stereo": self.lr[b % 2], "rds_clean": self.clean, "rds_bits": bits,
+                "rds_nbits": nbits}
+        rows = max_bytes // (4 * sum(t[0].numel() for t in outs.values()))
+        sel = None
+        if rows < self.nch:
+            sel = np.sort(np.random.Generator(np.random.PCG64(20240)).choice(self.nch, max(1, rows), replace=False))
+            idx = torch.from_numpy(sel).to(self.dev)
+            outs = {k: t.index_select(0, idx) for k, t in outs.items()}
+        res = {k: t.cpu().numpy().astype(np.float32) for k, t in outs.items()}
+        if sel is not None:
+            res["channels"] = sel.astype(np.float64)
+        return res
 
     def close(self) -> None:
         self.pipe.close()
@@ -716,6 +754,14 @@ def _digest(lr, bits) -> str:
     h.update(np.ascontiguousarray(lr).tobytes())
     h.update(np.ascontiguousarray(bits).tobytes())
     return h.hexdigest()
+
+
+def write_outputs(directory: str, outs: dict) -> None:
+    """--dump-outputs DIR: one DIR/<name>.npy per output array of the last timed step."""
+    d = pathlib.Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in outs.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def _pll_counters() -> dict | None:
@@ -892,10 +938,17 @@ def run_rank(args, world: int, rank: int, local: int, stepper_factory=None, back
         win.check()
         if world > 1:
             elapsed = max_over_ranks(torch, dist, elapsed, gdev)
-        # ---- outside the timed region: parity of the outputs (every rank checks its own captured
-        # channels against the oracle; the receiving rank checks that the rows the gather delivered
-        # from each rank are the rows that rank produced)
-        cap = st.captured() if (not args.no_cpu_baseline and hasattr(st, "captured")) else None
+        # ---- outside the timed region. --dump-outputs: the last timed step's outputs (rank 0's shard)
+        dump = getattr(args, "dump_outputs", None)
+        if dump and rank == 0 and hasattr(st, "last_outputs"):
+            write_outputs(dump, st.last_outputs())
+        # everything below the result line's own figures runs with --full only.
+        # Parity of the outputs (every rank checks its own captured channels against the oracle; the
+        # receiving rank checks that the rows the gather delivered from each rank are the rows that
+        # rank produced)
+        full = bool(getattr(args, "full", False))
+        cpu_legs = full and not args.no_cpu_baseline
+        cap = st.captured() if (cpu_legs and hasattr(st, "captured")) else None
         ver = verify_captured(cap, _cpu_share() if world == 1 else max(1, _cpu_share() // 2)) if cap else None
         gathered_check = None
         if world > 1 and cap is not None:
@@ -923,6 +976,7 @@ def run_rank(args, world: int, rank: int, local: int, stepper_factory=None, back
                 "n_gpus": world,
                 "steps": args.steps,
                 "warmup": args.warmup,
+                "full": full,
                 "ms_per_step": round(elapsed / args.steps * 1e3, 4),
                 "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
                 "higher_is_better": True,
@@ -947,15 +1001,16 @@ def run_rank(args, world: int, rank: int, local: int, stepper_factory=None, back
             res.update(st.report(args.warmup, elapsed, args.steps))
             if bg is not None:
                 res["gathered"] = bg.check_last(world)
-            if not args.no_isolated and hasattr(st, "isolated_frontend"):
+            if full and not args.no_isolated and hasattr(st, "isolated_frontend"):
                 iso = st.isolated_frontend()
                 res["frontend_isolated"] = iso
                 res["roofline"]["copy_GBps"] = iso["hbm_copy"]["achieved"]
                 res["roofline"]["frac_of_copy"] = round(res["roofline"]["achieved"] / iso["hbm_copy"]["achieved"], 4)
                 res["roofline_fast"] = iso.get("fast")
-            res["cpu_baseline"] = (None if args.no_cpu_baseline else cpu_baseline_leg(args, None, timing=(world == 1 and getattr(args, "cpu_timing", True))))
+            res["cpu_baseline"] = (cpu_baseline_leg(args, None, timing=(world == 1 and getattr(args, "cpu_timing", True)))
+                                   if cpu_legs else None)
             # the queue-plumbed program on the same input (N = 1, outside the timed region)
-            if (world == 1 and not args.no_cpu_baseline and hasattr(st, "captured") and
+            if (world == 1 and cpu_legs and hasattr(st, "captured") and
                     os.environ.get("SDR_BENCH_QUEUE", "1") != "0"):
                 res["queue_plumbed"] = qp = queue_plumbed_leg(args, st, nch)
                 if "value" in qp:
@@ -1296,12 +1351,14 @@ def queue_plumbed_leg(args, st, nch: int) -> dict:
     RDS bits compared with the bench's own captures of the same channels (which the checker compared
     with the oracle): equal rows mean the queue program is verified against the oracle too."""
     import tempfile
-    cap = st.captured()
+    # the blocks before the bench's input wraps (INPUT_RING): the child regenerates those in order
+    nb = st.ring
+    cap = {k: (v[:nb] if k in ("iq", "lr", "bits", "nbits") else v) for k, v in st.captured().items()}
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "cap.npz")
         cus = int(st.cu_spec) if str(getattr(st, "cu_spec", "")).isdigit() else 64
         cmd = [sys.executable, str(pathlib.Path(__file__).resolve()), "--queue-child", "--channels", str(nch),
-               "--blocks", str(st.nblocks), "--cus", str(cus), "--cap-ch", ",".join(str(c) for c in cap["channels"]),
+               "--blocks", str(nb), "--cus", str(cus), "--cap-ch", ",".join(str(c) for c in cap["channels"]),
                "--cap-out", out]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -1352,9 +1409,15 @@ def main() -> None:
     # (profiles/r04/warmup_ab.txt: 20 steps 0.720 ms after 5 warm-up blocks, 0.700-0.702 after 40)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--channels", type=int, default=1024, help="channels per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the oracle check of the captured channels, the CPU "
+                         "baselines, the isolated front-end and copy timings, the queue-plumbed receiver")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's channels) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU legs, the oracle check and the queue-plumbed receiver")
     ap.add_argument("--no-gather", action="store_true", help="skip the per-step RCCL gather (N>1)")
-    ap.add_argument("--no-isolated", action="store_true", help="skip the isolated front-end timings")
+    ap.add_argument("--no-isolated", action="store_true", help="with --full: skip the isolated front-end timings")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help=argparse.SUPPRESS)
     ap.add_argument("--numerics", choices=("exact", "fast"), default="exact",
                     help="exact: every output bit-identical to the reference; fast: the matrix-core front end "

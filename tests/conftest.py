@@ -52,7 +52,10 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def golden():
-    return dict(np.load(GOLD / "golden_mode0.npz"))
+    # two files (each below 1 MiB): outputs, hashes and taps; channel 0's per-block intermediates
+    g = dict(np.load(GOLD / "golden_mode0.npz"))
+    g.update(np.load(GOLD / "golden_mode0_inter.npz"))
+    return g
 
 
 @pytest.fixture(scope="session")

@@ -7,7 +7,8 @@ fixtures are data: inputs are regenerated from real-time-sdr_amd/synth.py (their
 stored) and the outputs are what the reference computes on them.
 
   golden_mode0.npz        mode 0, channels 0 and 3, 24 blocks: taps, per-block SHA-256 of every
-                          output, full arrays for blocks 0-3, intermediates for blocks 0, 1, 7 (ch 0)
+                          output, full arrays for blocks 0-3
+  golden_mode0_inter.npz  the same run's intermediates for blocks 0, 1, 7 (ch 0)
   golden_mode0_long.json  mode 0, channels 0 and 3, 200 blocks (6.1 s, PLL phase > 2^21 rad):
                           per-block cdr offset, symbols, decoded RDS bits, output hashes, RDS text
   project_e2e.json        the real reference program `project 0 m|s|r` on channel 0's input:
@@ -176,7 +177,10 @@ def main() -> None:
                 assert e2e["r"]["stderr"] == short["rds_text"], "RDS text of project 0 r != harness"
                 (GOLD / "project_e2e.json").write_text(json.dumps(e2e, indent=1) + "\n")
         (GOLD / "golden_modes123.json").write_text(json.dumps(make_modes(tmp), indent=0) + "\n")
+    dumped = tuple(f"ch{CHANNELS[0]}_b{b}_" for b in DUMP_BLOCKS)
+    inter = {k: npz.pop(k) for k in list(npz) if k.startswith(dumped)}
     np.savez_compressed(GOLD / "golden_mode0.npz", **npz)
+    np.savez_compressed(GOLD / "golden_mode0_inter.npz", **inter)   # apart: each file stays below 1 MiB
     (GOLD / "golden_mode0_long.json").write_text(json.dumps(long_fix, indent=0) + "\n")
     print("wrote", sorted(p.name for p in GOLD.iterdir()))
 

@@ -39,7 +39,7 @@ def _worker(rank: int, port: int, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD),
                       LOCAL_RANK="0", SDR_BENCH_CPU_CORES="4")
     import bench
-    args = argparse.Namespace(channels=NCH, warmup=WARMUP, steps=STEPS, no_gather=False, no_isolated=True,
+    args = argparse.Namespace(channels=NCH, warmup=WARMUP, steps=STEPS, full=True, no_gather=False, no_isolated=True,
                               no_cpu_baseline=False, numerics="exact", gpus=WORLD, backend="gloo")
     try:
         res = bench.run_rank(args, WORLD, rank, 0, backend="gloo")

@@ -5,7 +5,7 @@ TAG=${TAG:-b2}
 O=gpurun_out/$TAG
 mkdir -p $O
 for m in ${MODES:-fast exact}; do
-  timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --numerics $m ${BARGS:-} > $O/bench_$m.json 2> $O/bench_$m.err
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 3 --numerics $m ${BARGS:-} > $O/bench_$m.json 2> $O/bench_$m.err
   rc=$?; echo "bench $m rc=$rc"; cat $O/bench_$m.json; [ $rc -eq 0 ] || { tail -20 $O/bench_$m.err; exit $rc; }
 done
 if [ -n "$PROF" ]; then

@@ -9,6 +9,6 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_pipeline.py -x -q -k "golde
 tail -1 $O/fe_tests.log
 TAG=${TAG:-feq} bash tools/gpu/fe_ab.sh || exit 1
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench.json'));print(d['value'],d['ms_per_step'],d['roofline']['avg_launch_ms'],d['pll']['avg_launch_ms'],d['pll'].get('timeline'))"
 fi

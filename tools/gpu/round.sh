@@ -20,7 +20,7 @@ if [ "${TESTS:-1}" = 1 ]; then
 fi
 if [ "${BENCH:-1}" = 1 ]; then
   step bench
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; rc=$?
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; rc=$?
   cat $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; exit $rc; }
 fi
 if [ "${PROF:-1}" = 1 ]; then
