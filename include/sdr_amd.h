@@ -150,6 +150,33 @@ int sdr_frontend_times(sdr_ctx *ctx, double *ms, int max, int *n);
 /* The same launches' earliest workgroup start and latest end as raw 100 MHz device ticks (the clock
  * of sdr_plls_timeline), stamping front ends only: where each block's front end sat in the pipeline. */
 int sdr_frontend_stamps(sdr_ctx *ctx, unsigned long long *t_start, unsigned long long *t_end, int max, int *n);
+
+/* ---- shared-capture tuner (sdr_version >= 2): many stations from one I/Q stream per front end.
+ * Channel ch listens to row src[ch] of a batch of nsrc captures at the mode's rf_Fs and to the station
+ * khz[ch] kHz off that capture's centre. With N = rf_Fs / 1000 (2400, 1440, 2400, 1152 for modes 0..3)
+ * and n the absolute sample index (block * block_iq + index in the block; the 100 history samples in
+ * front of a block are the source row's previous samples, u8 128 before the first block), sample n is
+ * multiplied by the rotator T[(khz n) mod N] = (c, s):
+ *     y_I = fl(fl(x_I c) + fl(x_Q s)),  y_Q = fl(fl(x_Q c) - fl(x_I s)),  x = (u8 - 128) / 128
+ * (four f32 products, two f32 sums, no FMA: (I + jQ) e^(-j 2 pi khz n / N), the station lands at
+ * 0 Hz), then the front end's FIR and discriminator as ever. khz = 0 is the identity, bit for bit.
+ * The tuned front end always uses these exact numerics: with SDR_FLAG_FAST_FRONTEND it still runs the
+ * exact tuned kernel (int8 MFMA operands do not survive the mixer).
+ *
+ * host only, no GPU: the rotator table of a mode; *n = N, cs = [N][2] (cos, sin)(2 pi i / N), the real
+ * values correctly rounded to f32, when cs != NULL and max_pairs >= N */
+int sdr_tuner_table(int mode, float *cs, int max_pairs, int *n);
+/* src, khz: host arrays [nch]. nsrc rows of capture, 1 <= nsrc <= nch, 0 <= src[ch] < nsrc,
+ * -N/2 < khz[ch] <= N/2. Only on a context at block 0 (after create / sdr_ctx_reset); nsrc = 0 removes
+ * the tuning. The tuning survives sdr_ctx_reset (it is configuration, like the mode). Synchronises
+ * `stream`. A tuned context refuses sdr_frontend and sdr_frontend_pre_parts (SDR_E_INVALID: they would
+ * misread the rows); it runs the first block of a persistent launch as sdr_frontend_tuned + sdr_pre +
+ * sdr_plls_signal. */
+int sdr_tuner_set(sdr_ctx *ctx, int nsrc, const int32_t *src, const int32_t *khz, void *stream);
+int sdr_tuner_get(const sdr_ctx *ctx, int *nsrc);          /* 0: not tuned */
+/* RF_frontend loop body for a tuned context: iq [nsrc][2*block_iq]. Same parity-release wait, timing
+ * hooks (sdr_frontend_timing armed after sdr_tuner_set) and block advance as sdr_frontend. */
+int sdr_frontend_tuned(sdr_ctx *ctx, const uint8_t *iq, size_t iq_stride, void *stream);
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */

@@ -82,6 +82,10 @@ def lib() -> C.CDLL:
         "sdr_ctx_info": ([vp, C.POINTER(Info)], i32),
         "sdr_frontend": ([vp, vp, sz, vp], i32),
         "sdr_frontend_release_wait": ([vp, vp], i32),
+        "sdr_tuner_table": ([i32, vp, i32, C.POINTER(i32)], i32),
+        "sdr_tuner_set": ([vp, i32, vp, vp, vp], i32),
+        "sdr_tuner_get": ([vp, C.POINTER(i32)], i32),
+        "sdr_frontend_tuned": ([vp, vp, sz, vp], i32),
         "sdr_frontend_timing": ([vp, i32], i32),
         "sdr_frontend_times": ([vp, C.POINTER(C.c_double), i32, C.POINTER(i32)], i32),
         "sdr_frontend_stamps": ([vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), i32, C.POINTER(i32)], i32),
@@ -188,6 +192,19 @@ def impulse_response_rrc(Fs, num_taps):
     return _taps(lib().sdr_impulse_response_rrc, num_taps, Fs, num_taps)
 
 
+def tuner_table(mode: int):
+    """The shared-capture tuner's rotator table of a mode (host only): [N, 2] f32 (cos, sin)(2 pi i / N),
+    N = rf_Fs / 1000, each the real value correctly rounded (sdr_tuner_table)."""
+    import numpy as np
+    n = C.c_int(0)
+    if lib().sdr_tuner_table(mode, None, 0, C.byref(n)) != SDR_OK:
+        raise SdrError(f"sdr_tuner_table: mode {mode} not in 0..3", -1)
+    t = np.zeros((n.value, 2), np.float32)
+    if lib().sdr_tuner_table(mode, t.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) != SDR_OK:
+        raise SdrError("sdr_tuner_table failed", -1)
+    return t
+
+
 # ------------------------------------------------------------------ batched primitives (torch tensors)
 def convolve_fir(y, x, h, state, D: int, stream=None):
     """convolveFIR(y, x, h, state, D) for every row: y[nch][nx/D], x[nch][nx], state[nch][>=ntaps-1]."""
@@ -290,6 +307,36 @@ class Pipeline:
     def frontend(self, iq, stream=None):
         """iq: uint8 [nch][2*block_iq] (device)."""
         check(lib().sdr_frontend(self._h, _ptr(iq), _row_stride(iq), _stream(stream)), "sdr_frontend")
+
+    # shared-capture tuner (include/sdr_amd.h): channel ch = row src[ch] of the capture batch, shifted by khz[ch]
+    def set_tuning(self, src, khz, nsrc=None, stream=None):
+        """Tune the context (only at block 0): src, khz are [nch] integer sequences; nsrc defaults to
+        max(src) + 1. frontend_tuned(iq [nsrc][2*block_iq]) then replaces frontend()."""
+        import numpy as np
+        src = np.ascontiguousarray(src, np.int32)
+        khz = np.ascontiguousarray(khz, np.int32)
+        if src.shape != (self.nch,) or khz.shape != (self.nch,):
+            raise SdrError(f"set_tuning: src and khz must have {self.nch} entries", -1)
+        if nsrc is None:
+            nsrc = int(src.max()) + 1
+        check(lib().sdr_tuner_set(self._h, int(nsrc), src.ctypes.data_as(C.c_void_p), khz.ctypes.data_as(C.c_void_p),
+                                  _stream(stream)), "sdr_tuner_set")
+
+    def clear_tuning(self, stream=None):
+        check(lib().sdr_tuner_set(self._h, 0, None, None, _stream(stream)), "sdr_tuner_set")
+
+    @property
+    def nsrc(self) -> int:
+        """Source rows of the tuning, 0: not tuned."""
+        n = C.c_int(0)
+        check(lib().sdr_tuner_get(self._h, C.byref(n)), "sdr_tuner_get")
+        return n.value
+
+    def frontend_tuned(self, iq, stream=None):
+        """iq: uint8 [nsrc][2*block_iq] (device), the capture rows of a tuned context."""
+        # (a single row's stride is never used, and a view of one may report any)
+        stride = _row_stride(iq) if iq.shape[0] > 1 else int(iq.shape[1])
+        check(lib().sdr_frontend_tuned(self._h, _ptr(iq), stride, _stream(stream)), "sdr_frontend_tuned")
 
     def release_wait(self, stream=None):
         """The parity-release wait of the next frontend(), enqueued now on `stream` (that call then

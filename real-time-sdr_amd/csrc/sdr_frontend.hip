@@ -608,6 +608,215 @@ __global__ __launch_bounds__(64) void k_frontend2(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Tuned front end (sdr_frontend_tuned): channel ch listens to source row src[ch] and is shifted by
+// khz[ch] kHz before the same FIR and discriminator. With N = rf_Fs / 1000 (2400, 1440, 1152 for
+// D = 10, 4, 3) sample n of the stream is multiplied by T[(khz n) mod N] = (cos, sin)(2 pi i / N):
+//   y_I = fl(fl(x_I c) + fl(x_Q s)),  y_Q = fl(fl(x_Q c) - fl(x_I s))       (no FMA)
+// Same tile scheme as k_frontend2 (64 lanes, R outputs per lane, tiles advance by 64 R - 1), but the
+// staging phase converts and rotates every sample of the tile's window ONCE and keeps it in LDS as
+// an f32 pair; the FIR sweep then reads f32 pairs (no per-lane conversion). Samples are kept as
+// u8 - 128 (not / 128) against taps pre-scaled by 2^-7 like k_frontend2's: the power of two
+// commutes with every rounding of the mixer and of the products (nothing here is near the
+// subnormal range), so the sums are the reference's bit for bit.
+// Rotator: the quarter table Q[k] = RN32(cos(2 pi k / N)), 0 <= k <= N/4, in LDS (2.4 KiB for
+// N = 2400); cos and sin of any index follow by the quadrant symmetries (sin(k) = Q[N/4 - k]), the
+// same rule the host uses for sdr_tuner_table, so both hold the same values. The index advances
+// incrementally (an add and an unsigned minimum per step; one constant modulus per lane and tile).
+// Measured and dropped: the first half of the table as (cos, sin) pairs in LDS (9.4 KiB, one 8-byte
+// read and a sign flip per sample, fewer VALU instructions but 5 instead of 6 waves per CU):
+// 0.206 against 0.188 ms for 1024 channels on 128 rows (profiles/r07/tuner/).
+// Measured and dropped too: 16 bytes of LDS padding after every R D samples, so that the 16 lanes of
+// one pass of a 16-byte window read (lane stride 320 bytes at D = 10, four lanes per bank group)
+// cover 64 different banks: 0.191 against 0.188 ms, no gain -- the LDS reads do not bound the kernel.
+// Grid: logical workgroup L = pos * tiles + j, pos the channel's place in the order sorted by
+// source row, so the stations of one row are neighbours; hardware workgroup b runs L = (b % nxcc) *
+// per + b / nxcc because consecutive workgroups are dealt round-robin over the XCCs (sdr_internal.h,
+// CuPlacement) and each XCC has its own L2: one XCC then runs consecutive L, fetches a row's window
+// from HBM once and serves its other stations from its L2.
+// LDS: 8 bytes per staged sample, 80 bytes per output at D = 10. R = 4: 23.6 KiB per workgroup, 6
+// waves per CU of the 160 KiB; R = 8 (the untuned kernel's): 44 KiB, 3 waves per CU, fewer than one
+// per SIMD. SDR_TN_R selects it for A/B builds.
+// ------------------------------------------------------------------------------------------
+#ifndef SDR_TN_R
+#define SDR_TN_R 4
+#endif
+constexpr int TN_R = SDR_TN_R;
+constexpr int TN_PFC = 4;          // 16-byte LDS chunks (2 samples) read this many ahead of their use
+constexpr int tn_n(int D) { return D == 10 ? 2400 : D == 4 ? 1440 : 1152; }
+
+// The FIR sweep over an f32 window: as fe_fir (descending samples, taps in SGPRs), samples read
+// from LDS as (I, Q) f32 pairs, two per 16-byte chunk.
+template <int R, int D>
+__device__ __forceinline__ void tn_fir(const float* __restrict__ sy, const float* __restrict__ hs, f32x2 (&acc)[R]) {
+    constexpr int NT = 101, HP = NT - 1;
+    constexpr int TWIN = (R - 1) * D + NT;            // samples one thread reads
+    constexpr int TCH = (TWIN + 1) / 2;               // 16-byte LDS chunks per thread window
+    static_assert((R * D) % 2 == 0 && R % 2 == 0, "lane windows start on 16-byte chunks; taps come in pairs");
+    static_assert(TCH > TN_PFC, "prefetch depth");
+    const int t = threadIdx.x;
+    float4 chunk[TCH];
+    const float4* tw = reinterpret_cast<const float4*>(sy + 2 * t * R * D);
+#pragma unroll
+    for (int q = 1; q <= TN_PFC; q++) chunk[TCH - q] = tw[TCH - q];
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = f32x2{0.0f, 0.0f};
+    int zero = 0;                                     // (opaque, then uniform again: see fe_fir)
+    asm volatile("" : "+s"(zero));
+    zero = __builtin_amdgcn_readfirstlane(zero);
+    const double* hsd = reinterpret_cast<const double*>(hs) + zero;
+    double ring[FE_PF][R / 2];
+#pragma unroll
+    for (int jj = 0; jj < FE_PF; jj++) {
+        const int S0 = TWIN - 1 - jj;
+#pragma unroll
+        for (int q = 0; q < R / 2; q++) ring[S0 % FE_PF][q] = hsd[S0 * (R / 2) + q];
+    }
+#pragma unroll
+    for (int S = TWIN - 1; S >= 0; S--) {
+        const int slot = S % FE_PF;
+        if (((S & 1) == 1 || S == TWIN - 1) && (S >> 1) >= TN_PFC) chunk[(S >> 1) - TN_PFC] = tw[(S >> 1) - TN_PFC];
+        const float4 c4 = chunk[S >> 1];
+        const f32x2 m = (S & 1) ? f32x2{c4.z, c4.w} : f32x2{c4.x, c4.y};
+        f32x2 prod[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const int k = r * D + HP - S;
+            if (k >= 0 && k < NT) prod[r] = fe_mul_v(ring[slot][r >> 1], r & 1, m);
+        }
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const int k = r * D + HP - S;
+            if (k >= 0 && k < NT) acc[r] = fe_add_v(acc[r], prod[r]);
+        }
+        if (S - FE_PF >= 0) {
+#pragma unroll
+            for (int q = 0; q < R / 2; q++) ring[slot][q] = hsd[(S - FE_PF) * (R / 2) + q];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// tune[pos] = {channel, source row, khz mod N, 1: this channel stores its row's tail}
+template <int R, int D>
+__global__ __launch_bounds__(64) void k_frontend_tuned(
+    const uint8_t* __restrict__ iq, size_t iq_stride, const uint8_t* __restrict__ tail_in,
+    uint8_t* __restrict__ tail_out, const float2* __restrict__ prev_in, float2* __restrict__ prev_out,
+    const float* __restrict__ hs, const float* __restrict__ qtab, const int4* __restrict__ tune, int phase0,
+    int block_iq, int block_if, float* __restrict__ fm, const float* __restrict__ fm_other, size_t fm_stride,
+    int tiles, int total, int per, int nxcc, const uint32_t* __restrict__ pad, unsigned long long* __restrict__ stamps) {
+    constexpr int NT = 101, HP = NT - 1, NTH = 64;
+    constexpr int N = tn_n(D), Q4 = N / 4;
+    if (stamps && threadIdx.x == 0) stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+    constexpr int TILE = NTH * R;
+    constexpr int ADV = TILE - 1;
+    constexpr int WIN = (TILE - 1) * D + NT;          // staged samples
+    constexpr int NP = (WIN + 1) / 2;                 // sample pairs (16-byte LDS chunks)
+    constexpr int PER = (NP + NTH - 1) / NTH;         // pairs per lane
+    __shared__ __attribute__((aligned(16))) float4 sy4[NP];
+    __shared__ float sq[Q4 + 1];
+    const int t = threadIdx.x;
+    const int b = (int)blockIdx.x;
+    const int L = (b % nxcc) * per + b / nxcc;
+    if (L >= total) {                                 // the grid is rounded up to whole XCC shares
+        if (stamps && t == 0) stamps[2 * b + 1] = __builtin_amdgcn_s_memrealtime();
+        return;
+    }
+    const int pos = L / tiles, j = L - pos * tiles;
+    const int4 tn = tune[pos];
+    const int ch = tn.x, srow = tn.y, kpos = tn.z;
+    const int c0 = j * ADV - 1;                       // first decimated output (the carry)
+    const int m0 = c0 * D - HP;                       // first staged sample (>= -D - HP)
+    const uint8_t* src = iq + (size_t)srow * iq_stride;
+    const uint8_t* tin = tail_in + (size_t)srow * 2 * HP;
+    for (int i = t; i <= Q4; i += NTH) sq[i] = qtab[i];
+    // ---- the window's u8 pairs -> registers (one dword = two samples per lane and step)
+    uint32_t pf[PER];
+    const bool interior = m0 >= 0 && m0 + 2 * NP <= block_iq;
+    if (interior && (reinterpret_cast<uintptr_t>(src + 2 * m0) & 3) == 0) {
+        const uint32_t* g = reinterpret_cast<const uint32_t*>(src + 2 * m0);
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int i = t + NTH * k;
+            pf[k] = (k < PER - 1 || i < NP) ? g[i] : 0x80808080u;
+        }
+    } else {
+        // per sample from the block, the row's tail (the 100 samples before the block) or u8 128
+        const uint16_t* s16 = reinterpret_cast<const uint16_t*>(src);
+        const uint16_t* t16 = reinterpret_cast<const uint16_t*>(tin);
+        const uint16_t* p16 = reinterpret_cast<const uint16_t*>(pad);
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int i = t + NTH * k;
+            uint32_t v = 0x80808080u;
+            if (k < PER - 1 || i < NP) {
+                v = 0;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int m = m0 + 2 * i + h;
+                    const uint16_t* pa = (m >= 0 && m < block_iq) ? s16 + m : (m < 0 && m >= -HP) ? t16 + (HP + m) : p16;
+                    v |= (uint32_t)*pa << (16 * h);
+                }
+            }
+            pf[k] = v;
+        }
+    }
+    __syncthreads();                                  // the table is in LDS
+    // ---- convert, rotate, store. Sample m of the block is sample n = B block_iq + m of the stream;
+    // nn = n mod N of this lane's first sample (phase0 = (B block_iq) mod N, m0 + N > 0), idx = (khz n) mod N
+    {
+        const uint32_t nn = (uint32_t)(phase0 + m0 + 2 * t + N) % (uint32_t)N;
+        int idxA = (int)(((uint32_t)kpos * nn) % (uint32_t)N);
+        const int step = (int)(((uint32_t)kpos * (2u * NTH)) % (uint32_t)N);
+        // (c, s) of index i by the quadrant symmetries (0 - x: a zero stays +0, as in sdr_tuner_table)
+        auto rot = [&](uint32_t i, float& c, float& sn) {
+            const int q = (i >= 2u * Q4) ? ((i >= 3u * Q4) ? 3 : 2) : ((i >= (uint32_t)Q4) ? 1 : 0);
+            const int r = (int)i - q * Q4;
+            const float a = sq[r], bq = sq[Q4 - r];   // cos and sin of 2 pi r / N
+            c = (q & 1) ? bq : a;
+            sn = (q & 1) ? a : bq;
+            if (q == 1 || q == 2) c = 0.0f - c;
+            if (q >= 2) sn = 0.0f - sn;
+        };
+        uint32_t ia = (uint32_t)idxA;
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int i = t + NTH * k;
+            const uint32_t ib = min(ia + (uint32_t)kpos, ia + (uint32_t)kpos - (uint32_t)N);
+            const uint32_t w = pf[k] ^ 0x80808080u;               // u8 - 128 as signed bytes
+            const f32x2 x0 = fe_cvt_v<0>(w), x1 = fe_cvt_v<1>(w);
+            float c0f, s0f, c1f, s1f;
+            rot(ia, c0f, s0f);
+            rot(ib, c1f, s1f);
+            float4 o;
+            o.x = x0.x * c0f + x0.y * s0f;
+            o.y = x0.y * c0f - x0.x * s0f;
+            o.z = x1.x * c1f + x1.y * s1f;
+            o.w = x1.y * c1f - x1.x * s1f;
+            if (k < PER - 1 || i < NP) sy4[i] = o;
+            ia = min(ia + (uint32_t)step, ia + (uint32_t)step - (uint32_t)N);
+        }
+    }
+    __syncthreads();
+    f32x2 acc[R];
+    tn_fir<R, D>(reinterpret_cast<const float*>(sy4), hs, acc);
+    float* out = fm + (size_t)ch * fm_stride;
+    fe_disc_store<R>(acc, c0, ch, prev_in, prev_out, out, block_if);
+    if (j == 0) {
+        if (tn.w) {                                   // one channel per source row keeps the row's tail
+            const uint16_t* last = reinterpret_cast<const uint16_t*>(src) + (block_iq - HP);
+            uint16_t* tout = reinterpret_cast<uint16_t*>(tail_out + (size_t)srow * 2 * HP);
+            for (int i = t; i < HP; i += NTH) tout[i] = last[i];
+        }
+        const float* o = fm_other + (size_t)ch * fm_stride;
+        for (int i = t; i < HIST; i += NTH) out[i - HIST] = o[block_if - HIST + i];
+    }
+    if (stamps) {   // the end: after this wave's stores have completed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (threadIdx.x == 0) stamps[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+    }
+}
+
 size_t frontend_lds_bytes(int ntaps, int tile, int D) {
     const int ntaps_pad = (ntaps + 3) & ~3;
     const int W = tile * D + ntaps;                  // window incl. the extra output at n0-1
@@ -674,6 +883,36 @@ int frontend_launch(const FrontendArgs& a, hipStream_t s, int j0, int jn) {
                               a.fm_stride);
     }
 #undef FE2
+    LAUNCH_CHECK();
+    return SDR_OK;
+}
+
+// ---- tuned front end
+int frontend_tuned_r() { return TN_R; }
+int frontend_tuned_n(int D) { return tn_n(D); }
+static int tuned_tiles(int block_if) { return cdiv(block_if + 1, 64 * TN_R - 1); }
+// hardware workgroups: the logical ones rounded up to whole XCC shares (k_frontend_tuned)
+int frontend_tuned_wgs(int block_if, int nch, int nxcc) {
+    nxcc = std::max(nxcc, 1);
+    return cdiv(tuned_tiles(block_if) * nch, nxcc) * nxcc;
+}
+
+int frontend_tuned_launch(const FrontendArgs& a, const float* ht, const float* qtab, const int32_t* tune, int phase0,
+                          int nxcc, hipStream_t s) {
+    if (a.ntaps != 101 || (a.D != 10 && a.D != 4 && a.D != 3))
+        return fail(SDR_E_INVALID, "frontend_tuned: needs 101 taps and a decimation of 10, 4 or 3");
+    nxcc = std::max(nxcc, 1);
+    const int tiles = tuned_tiles(a.block_if), total = tiles * a.nch, per = cdiv(total, nxcc);
+    const dim3 g(per * nxcc);
+    const int4* tn = reinterpret_cast<const int4*>(tune);
+#define FET(DD)                                                                                                   \
+    hipLaunchKernelGGL((k_frontend_tuned<TN_R, DD>), g, dim3(64), 0, s, a.iq, a.iq_stride, a.tail_in, a.tail_out,    \
+                       a.prev_in, a.prev_out, ht, qtab, tn, phase0, a.block_iq, a.block_if, a.fm, a.fm_other,         \
+                       a.fm_stride, tiles, total, per, nxcc, a.pad80, a.stamps)
+    if (a.D == 10) FET(10);
+    else if (a.D == 4) FET(4);
+    else FET(3);
+#undef FET
     LAUNCH_CHECK();
     return SDR_OK;
 }

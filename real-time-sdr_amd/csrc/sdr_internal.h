@@ -112,6 +112,15 @@ int frontend_tiles(int block_if);   // exact front-end tiles per channel and blo
 int frontend_tab_r();               // outputs per lane of the exact front end (tap-table row length)
 // workgroups of a whole-block launch that stamps itself (sdr_frontend_timing), 0: the kernel does not
 int frontend_stamp_wgs(int block_if, int nch, int ntaps, int D, bool fast);
+// tuned front end (k_frontend_tuned): a.iq holds the source rows, a.tail_* are per source row.
+// ht: the tap table for frontend_tuned_r() outputs per lane (rows as rf_hs), qtab: the rotator's quarter
+// table [N/4 + 1] (cosines), tune: [nch][4] = {channel, source row, khz mod N, tail writer} in grid order,
+// phase0 = (block * block_iq) mod N, nxcc: XCCs of the device
+int frontend_tuned_launch(const FrontendArgs& a, const float* ht, const float* qtab, const int32_t* tune, int phase0,
+                          int nxcc, hipStream_t s);
+int frontend_tuned_r();
+int frontend_tuned_n(int D);        // N = rf_Fs / 1000 of the decimation's mode
+int frontend_tuned_wgs(int block_if, int nch, int nxcc);   // workgroups (and stamp pairs) of a tuned launch
 
 // ---- sdr_pll.hip
 int launch_nco(const PllJobs& jobs, int njobs, int n, int nch, hipStream_t s);
@@ -211,6 +220,10 @@ struct sdr_ctx {
     void* fe_afrag = nullptr;                           // MFMA front end: tap digit fragments
     double fe_yscale = 0.0;                             // 2^-(F+7): fixed-point taps, x = (u-128)/128
     int cus = 0;                                        // compute units of the device
+    // shared-capture tuner (sdr_tuner_set): nsrc source rows feed the nch channels; 0: not tuned
+    int tn_nsrc = 0, nxcc = 1;
+    float *rf_ht = nullptr, *tn_q = nullptr;            // tuned tap table, rotator quarter table [N/4 + 1]
+    int32_t* tn_tab = nullptr;                          // [nch][4] (frontend_tuned_launch)
     int parity = 1;                                     // parity of the current block
     long long block = -1;                               // index of the current block
     long long stereo_done = -1, rds_dsp_done = -1, rds_bits_done = -1, mono_done = -1;

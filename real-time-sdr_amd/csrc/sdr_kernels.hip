@@ -1708,7 +1708,7 @@ namespace {
 extern "C" {
 
 const char* sdr_last_error(void) { return sdrk::last_error(); }
-int sdr_version(void) { return 1; }
+int sdr_version(void) { return 2; }   // 2: the shared-capture tuner (sdr_tuner_*, sdr_frontend_tuned)
 
 int sdr_stream_create_cu_range(void** stream, int device, int first_cu, int n_cu, int exclude) {
     if (!stream) return fail(SDR_E_INVALID, "sdr_stream_create_cu_range: stream is NULL");
@@ -1856,6 +1856,29 @@ int sdr_ctx_create(sdr_ctx** out, int device, int nch, int mode, int rds_on, int
                 if (k >= 0 && k < T) tt[(size_t)S_ * R + r] = rf[k] * 0.0078125f;
             }
         TRY(upload(c, &c->rf_hs, tt));
+    }
+    if (T == 101 && (in.rf_decim == 10 || in.rf_decim == 4 || in.rf_decim == 3)) {
+        // tuned front end (sdr_frontend_tuned): the same table for its outputs per lane, and the
+        // rotator's quarter table (the first quadrant's cosines of sdr_tuner_table); the tuning itself
+        // comes with sdr_tuner_set
+        const int R = frontend_tuned_r(), D = in.rf_decim, TWIN = (R - 1) * D + T;
+        std::vector<float> tt((size_t)TWIN * R + 32, 0.0f);
+        for (int S_ = 0; S_ < TWIN; S_++)
+            for (int r = 0; r < R; r++) {
+                const int k = r * D + (T - 1) - S_;
+                if (k >= 0 && k < T) tt[(size_t)S_ * R + r] = rf[k] * 0.0078125f;
+            }
+        TRY(upload(c, &c->rf_ht, tt));
+        const int N = frontend_tuned_n(D);
+        std::vector<float> q((size_t)2 * N);
+        int nt = 0;
+        if (N != in.rf_Fs / 1000 || sdr_tuner_table(mode, q.data(), N, &nt) != SDR_OK || nt != N)
+            TRY(fail(SDR_E_INVALID, "tuner: no rotator table for rf_Fs %d", in.rf_Fs));
+        for (int k = 0; k <= N / 4; k++) q[(size_t)k] = q[(size_t)2 * k];   // cos(2 pi k / N)
+        q.resize((size_t)N / 4 + 1);
+        TRY(upload(c, &c->tn_q, q));
+        TRY(dalloc(c, &c->tn_tab, (size_t)4 * nch));
+        c->nxcc = device_xccs(device);
     }
     if (T == 101 && (in.rf_decim == 10 || in.rf_decim == 4 || in.rf_decim == 3)) {
         // MFMA front end: taps as fixed point h*2^F in FT_ND balanced base-256 digits, laid out as
@@ -2120,6 +2143,7 @@ int sdr_frontend(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* stream) 
     if (!c || !iq) return fail(SDR_E_INVALID, "null argument");
     if (const int rf_ = check_failed(c, "frontend")) return rf_;
     if (const int r = check_iq(c, iq, iq_stride)) return r;
+    if (c->tn_nsrc > 0) return fail(SDR_E_INVALID, "frontend: the context is tuned (sdr_frontend_tuned)");
     const int p = c->parity ^ 1;
     // fm of parity p, and the pre stages' buffers too (one wait kernel: sdr_pre on this stream then
     // has nothing left to wait for; waiting for the RDS mixer only before the pre stages measured the
@@ -2141,11 +2165,80 @@ int sdr_frontend(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* stream) 
     return SDR_OK;
 }
 
+// ---- shared-capture tuner: channel ch = source row src[ch] shifted by khz[ch] kHz (sdr_frontend.hip)
+int sdr_tuner_set(sdr_ctx* c, int nsrc, const int32_t* src, const int32_t* khz, void* stream) {
+    if (!c) return fail(SDR_E_INVALID, "tuner_set: null context");
+    if (c->block != -1) return fail(SDR_E_INVALID, "tuner_set: only at block 0 (after create or sdr_ctx_reset)");
+    if (!c->tn_tab) return fail(SDR_E_INVALID, "tuner_set: the context has no tuned front end");
+    if (nsrc < 0 || nsrc > c->nch) return fail(SDR_E_INVALID, "tuner_set: nsrc %d outside [0, nch %d]", nsrc, c->nch);
+    c->fe_time_cap = c->fe_time_n = 0;   // (the timed launches' stamp layout belongs to the other kernel)
+    if (nsrc == 0) {
+        c->tn_nsrc = 0;
+        return SDR_OK;
+    }
+    if (!src || !khz) return fail(SDR_E_INVALID, "tuner_set: null src or khz");
+    const int N = c->info.rf_Fs / 1000;
+    for (int ch = 0; ch < c->nch; ch++) {
+        if (src[ch] < 0 || src[ch] >= nsrc)
+            return fail(SDR_E_INVALID, "tuner_set: src[%d] = %d outside [0, %d)", ch, (int)src[ch], nsrc);
+        if (2 * (long long)khz[ch] <= -(long long)N || 2 * (long long)khz[ch] > N)
+            return fail(SDR_E_INVALID, "tuner_set: khz[%d] = %d outside (-%d/2, %d/2]", ch, (int)khz[ch], N, N);
+    }
+    // grid order: channels sorted by source row (stable), so the stations of a row are neighbours;
+    // the first of each row stores the row's tail
+    std::vector<int> ord(c->nch);
+    for (int ch = 0; ch < c->nch; ch++) ord[ch] = ch;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return src[a] < src[b]; });
+    std::vector<int32_t> tab((size_t)4 * c->nch);
+    for (int pos = 0; pos < c->nch; pos++) {
+        const int ch = ord[pos];
+        tab[4 * pos + 0] = ch;
+        tab[4 * pos + 1] = src[ch];
+        tab[4 * pos + 2] = ((khz[ch] % N) + N) % N;
+        tab[4 * pos + 3] = (pos == 0 || src[ord[pos - 1]] != src[ch]) ? 1 : 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(c->tn_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, S(stream)));
+    HIP_TRY(hipStreamSynchronize(S(stream)));   // (tab is a local)
+    c->tn_nsrc = nsrc;
+    return SDR_OK;
+}
+
+int sdr_tuner_get(const sdr_ctx* c, int* nsrc) {
+    if (!c || !nsrc) return fail(SDR_E_INVALID, "tuner_get: null argument");
+    *nsrc = c->tn_nsrc;
+    return SDR_OK;
+}
+
+int sdr_frontend_tuned(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* stream) {
+    if (!c || !iq) return fail(SDR_E_INVALID, "null argument");
+    if (const int rf_ = check_failed(c, "frontend_tuned")) return rf_;
+    if (const int r = check_iq(c, iq, iq_stride)) return r;
+    if (c->tn_nsrc <= 0) return fail(SDR_E_INVALID, "frontend_tuned: the context is not tuned (sdr_tuner_set)");
+    const int p = c->parity ^ 1;
+    if (const int rw = release_wait(c, p, REL_MONO | REL_STEREO | REL_RDS, S(stream))) return rw;
+    FrontendArgs a = frontend_args(c, iq, iq_stride, p);   // (the tail rows are per source row here)
+    const bool timed = c->fe_time_n < c->fe_time_cap && c->fe_use_stamps &&
+                       c->fe_stamp_wgs == frontend_tuned_wgs(c->info.block_if, c->nch, c->nxcc);
+    if (timed) a.stamps = c->fe_stamps + (size_t)c->fe_time_n * c->fe_stamp_wgs * 2;
+    // the block being produced is c->block + 1: its first sample is sample (block * block_iq) of the stream
+    const long long N = c->info.rf_Fs / 1000;
+    const int phase0 = (int)((((c->block + 1) % N) * (c->info.block_iq % N)) % N);
+    const int r = frontend_tuned_launch(a, c->rf_ht, c->tn_q, c->tn_tab, phase0, c->nxcc, S(stream));
+    if (r) return r;
+    if (timed) c->fe_time_n++;
+    c->parity = p;
+    c->block++;
+    return SDR_OK;
+}
+
 int sdr_frontend_timing(sdr_ctx* c, int max_launches) {
     if (!c || max_launches < 0) return fail(SDR_E_INVALID, "frontend_timing: bad arguments");
     HIP_TRY(hipSetDevice(c->device));
     const sdr_info& in = c->info;
-    const int wgs = frontend_stamp_wgs(in.block_if, c->nch, c->ntaps, in.rf_decim, c->flags & SDR_FLAG_FAST_FRONTEND);
+    const int wgs = c->tn_nsrc > 0 ? frontend_tuned_wgs(in.block_if, c->nch, c->nxcc)
+                                   : frontend_stamp_wgs(in.block_if, c->nch, c->ntaps, in.rf_decim,
+                                                        c->flags & SDR_FLAG_FAST_FRONTEND);
     c->fe_use_stamps = wgs > 0;
     if (c->fe_use_stamps) {
         if (c->fe_stamp_cap < max_launches || c->fe_stamp_wgs != wgs) {
@@ -2736,6 +2829,7 @@ int sdr_frontend_pre_parts(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, int 
     if (!c || !iq || nparts < 1) return fail(SDR_E_INVALID, "frontend_pre_parts: bad arguments");
     if (const int rf_ = check_failed(c, "frontend_pre_parts")) return rf_;
     if (const int r = check_iq(c, iq, iq_stride)) return r;
+    if (c->tn_nsrc > 0) return fail(SDR_E_INVALID, "frontend_pre_parts: the context is tuned (the fill by parts is untuned-only)");
     if (!c->rds_on || c->ntaps != FRB_T || (c->flags & SDR_FLAG_FAST_FRONTEND))
         return fail(SDR_E_INVALID, "frontend_pre_parts: needs rds_on, 101 taps and the exact front end");
     if (c->pers_signaled != c->pers_base)

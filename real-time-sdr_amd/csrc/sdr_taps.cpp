@@ -103,3 +103,49 @@ extern "C" int sdr_impulse_response_rrc(float Fs, unsigned short num_taps, float
     }
     return SDR_OK;
 }
+
+// The shared-capture tuner's rotator table of a mode: T[i] = (cos, sin)(2 pi i / N), N = rf_Fs / 1000,
+// each the real value correctly rounded to f32. Only the first octant is evaluated (in extended
+// precision: the value's distance from an f32 rounding tie is then many orders above the evaluation
+// error; tests/test_tuner_model.py compares every entry with a 50-digit evaluation); the rest follows
+// by symmetry, so T[0] = (1, 0) and T[N/4] = (0, 1) exactly. A negated zero is written as 0 - x = +0.
+// The kernel keeps the first half (the second is the first negated).
+namespace {
+int tuner_n(int mode) { return mode == 0 || mode == 2 ? 2400 : mode == 1 ? 1440 : mode == 3 ? 1152 : 0; }
+}  // namespace
+
+// Q[k] = RN32(cos(2 pi k / n)), 0 <= k <= n/4; sin(2 pi k / n) = Q[n/4 - k]
+static int tuner_quarter(int n, float* q) {
+    if (n <= 0 || n % 8 || !q) return SDR_E_INVALID;
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    const int q4 = n / 4, q8 = n / 8;
+    for (int k = 0; k <= q8; k++) {
+        const long double a = two_pi * (long double)k / (long double)n;
+        q[k] = k == 0 ? 1.0f : (float)cosl(a);
+        q[q4 - k] = k == 0 ? 0.0f : (float)sinl(a);   // cos(pi/2 - a); k = n/8 writes cos last
+    }
+    q[q8] = (float)cosl(two_pi * (long double)q8 / (long double)n);
+    return SDR_OK;
+}
+
+extern "C" int sdr_tuner_table(int mode, float* cs, int max_pairs, int* n) {
+    const int N = tuner_n(mode);
+    if (N == 0 || !n) return SDR_E_INVALID;
+    if (cs && max_pairs < N) return SDR_E_INVALID;
+    *n = N;
+    if (!cs) return SDR_OK;
+    const int q4 = N / 4;
+    float* q = new float[q4 + 1];
+    tuner_quarter(N, q);
+    for (int i = 0; i < N; i++) {
+        const int qd = i / q4, r = i - qd * q4;
+        const float a = q[r], b = q[q4 - r];            // cos and sin of 2 pi r / N
+        float c = (qd & 1) ? b : a, s = (qd & 1) ? a : b;
+        if (qd == 1 || qd == 2) c = 0.0f - c;
+        if (qd >= 2) s = 0.0f - s;
+        cs[2 * i] = c;
+        cs[2 * i + 1] = s;
+    }
+    delete[] q;
+    return SDR_OK;
+}

@@ -1,24 +1,32 @@
 // sdr_multi.cpp -- multi-channel receiver CLI over the engine of include/sdr_multi.h (the reference
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
-//   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N]
+//   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE]
 //
 // Input: u8 I/Q, block after block, each block NCH rows of 2*block_iq bytes (channel after
 // channel: the [block][channel][bytes] layout of bench.py). Output: PREFIX.pcm -- per block NCH
 // rows of 2*n_audio int16 (L/R interleaved per channel, stereo.cpp:100-111) -- and PREFIX.rds, the
 // RDS text of every channel ("ch <c>: " + parse()'s lines, rds_utilities.cpp:172-199). --cus N: the
 // two consumers' PLLs on CUs [0, N) (persistent launches when the input is a regular file), 0: no
-// CU masks. A summary line goes to stderr.
+// CU masks. --tune FILE: shared captures (include/sdr_multi_tuned.h) -- FILE is text, one "src khz"
+// pair per line, NCH lines: channel c listens to capture row src and to the station khz kHz off its
+// centre; the input then holds max(src) + 1 rows per block instead of NCH. A summary line goes to
+// stderr.
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "sdr_amd.h"
 #include "sdr_multi.h"
+#include "sdr_multi_tuned.h"
 
 namespace {
 [[noreturn]] void usage() {
-    std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N]\n");
+    std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
+                         "[--tune FILE]\n"
+                         "  --tune FILE: NCH lines \"src khz\"; the input holds max(src)+1 capture rows per block\n");
     std::exit(1);
 }
 }  // namespace
@@ -28,7 +36,7 @@ int main(int argc, char** argv) {
     sdr_multi_opts o{};
     o.nch = std::atoi(argv[1]);
     o.pll_cus = 64;
-    std::string in = "-", out = "sdr_multi";
+    std::string in = "-", out = "sdr_multi", tune_path;
     if (o.nch <= 0) usage();
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
@@ -36,6 +44,7 @@ int main(int argc, char** argv) {
         else if (a == "--in" && i + 1 < argc) in = argv[++i];
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else if (a == "--cus" && i + 1 < argc) o.pll_cus = std::atoi(argv[++i]);
+        else if (a == "--tune" && i + 1 < argc) tune_path = argv[++i];
         else if (a == "--fast") o.flags |= SDR_FLAG_FAST_FRONTEND;
         else usage();
     }
@@ -43,9 +52,34 @@ int main(int argc, char** argv) {
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();
     sdr_multi_stats st{};
-    const int rc = sdr_multi_run(&o, &st);
+    std::vector<int32_t> src, khz;
+    sdr_multi_tuning tune{};
+    if (!tune_path.empty()) {
+        FILE* tf = std::fopen(tune_path.c_str(), "r");
+        if (!tf) {
+            std::fprintf(stderr, "sdr_multi: cannot open %s\n", tune_path.c_str());
+            return 1;
+        }
+        int a = 0, b = 0, extra = 0;
+        while ((int)src.size() < o.nch && std::fscanf(tf, "%d %d", &a, &b) == 2) {
+            src.push_back(a);
+            khz.push_back(b);
+            tune.nsrc = a + 1 > tune.nsrc ? a + 1 : tune.nsrc;
+        }
+        const bool more = std::fscanf(tf, "%d", &extra) == 1;
+        std::fclose(tf);
+        if ((int)src.size() != o.nch || more) {
+            std::fprintf(stderr, "sdr_multi: %s must hold %d lines \"src khz\"\n", tune_path.c_str(), o.nch);
+            return 1;
+        }
+        tune.src = src.data();
+        tune.khz = khz.data();
+    }
+    const int rows = tune_path.empty() ? o.nch : tune.nsrc;
+    const int rc = sdr_multi_run_tuned(&o, tune_path.empty() ? nullptr : &tune, &st);
     if (rc != SDR_OK) {
-        std::fprintf(stderr, "sdr_multi: %d %s\n", rc, sdr_last_error());
+        std::fprintf(stderr, "sdr_multi: %d %s%s\n", rc, sdr_last_error(),
+                     tune_path.empty() ? "" : " (--tune: 0 <= src < NCH rows, -N/2 < khz <= N/2, N = rf_Fs / 1000)");
         return 1;
     }
     sdr_ctx* probe = nullptr;   // sizes of the mode
@@ -54,17 +88,19 @@ int main(int argc, char** argv) {
     sdr_ctx_destroy(probe);
     const double samples = (double)st.blocks * o.nch * info.block_iq;
     const double signal_s = (double)st.blocks * info.block_iq / (double)info.rf_Fs;
-    const double in_gb = (double)st.blocks * o.nch * 2.0 * info.block_iq / 1e9;
+    const double in_gb = (double)st.blocks * rows * 2.0 * info.block_iq / 1e9;
     char after0[128] = "after block 0 n/a (fewer than 2 blocks)";
     if (st.blocks >= 2 && st.steady_seconds > 0)
         std::snprintf(after0, sizeof(after0), "after block 0 %.1f MS/s (%.1fx real time)",
                       (double)(st.blocks - 1) * o.nch * info.block_iq / st.steady_seconds / 1e6,
                       (double)(st.blocks - 1) * info.block_iq / (double)info.rf_Fs / st.steady_seconds);
+    char rows_txt[64] = "";   // a tuned run reads fewer rows than it has channels
+    if (!tune_path.empty()) std::snprintf(rows_txt, sizeof(rows_txt), " (from %d capture rows per block)", rows);
     std::fprintf(stderr,
-                 "sdr_multi: %d channels x %lld blocks in %.3f s: %.1f MS/s I/Q, %.1fx real time; %s; PLLs %s "
+                 "sdr_multi: %d channels%s x %lld blocks in %.3f s: %.1f MS/s I/Q, %.1fx real time; %s; PLLs %s "
                  "(%.4f ms per block); input read %.3f s (%.1f GB/s), H2D %.3f s GPU time (%.1f GB/s), "
                  "L/R D2H %.3f s\n",
-                 o.nch, st.blocks, st.seconds, st.seconds > 0 ? samples / st.seconds / 1e6 : 0.0,
+                 o.nch, rows_txt, st.blocks, st.seconds, st.seconds > 0 ? samples / st.seconds / 1e6 : 0.0,
                  st.seconds > 0 ? signal_s / st.seconds : 0.0, after0, st.persistent ? "persistent" : "per-block dispatch",
                  st.pll_period_ms, st.read_s, st.read_s > 0 ? in_gb / st.read_s : 0.0, st.h2d_ms / 1e3,
                  st.h2d_ms > 0 ? in_gb / (st.h2d_ms / 1e3) : 0.0, st.d2h_ms / 1e3);

@@ -7,7 +7,8 @@
 // Threads (per block b; every device hand-off is a HIP event or a device flag, no thread waits for
 // another's GPU work except through the queue's prepare() ordering):
 //   reader  file/stdin -> pinned ring slot (byte-stream input only)
-//   RF      [slot -H2D (copy stream)-> d_iq] or the device-resident block; sdr_frontend; fm_demod ->
+//   RF      [slot -H2D (copy stream)-> d_iq] or the device-resident block; sdr_frontend (a tuned run,
+//           include/sdr_multi_tuned.h: sdr_frontend_tuned on nsrc capture rows per block); fm_demod ->
 //           a recycled FmBatch (device), event, push                     rffrontend.cpp:45-76
 //   audio   wait_and_pop(0); sdr_push_fm_demod; stereo_pre; PLL; stereo_post; L/R -D2H-> pinned;
 //           the write of block b-1 overlaps the GPU work of block b          stereo.cpp:69-114
@@ -46,6 +47,7 @@
 #include "rds_utilities.h"
 #include "sdr_amd.h"
 #include "sdr_multi.h"
+#include "sdr_multi_tuned.h"
 
 using sdrhost::check_hip;
 using sdrhost::check_sdr;
@@ -275,6 +277,8 @@ struct RdsRes {
 
 struct Shared {
     sdr_multi_opts o{};
+    int rows = 0;                        // input rows per block: nch, or a tuned run's nsrc
+    bool tuned = false;
     AudioRes ar;
     RdsRes rr;
     hipStream_t s_d2h = nullptr;         // the L/R copies when not on s_post (SDR_MULTI_D2H=copy)
@@ -362,7 +366,7 @@ void rf_thread(Shared* sh) {
     sh->arrive_and_wait();
     sdr_ctx* ctx = sh->ctx[0];
     const sdr_info& in = sh->info;
-    const size_t row = 2 * (size_t)in.block_iq, bytes = row * o.nch;
+    const size_t row = 2 * (size_t)in.block_iq, bytes = row * (size_t)sh->rows;
     hipStream_t s = sh->s_fe;
     const bool dev_in = o.in_path == nullptr;
     uint8_t* d_iq[2] = {};
@@ -419,7 +423,8 @@ void rf_thread(Shared* sh) {
         if (b == 1) sh->t_block1 = std::chrono::steady_clock::now();
         const hipStream_t sf = fe_stream(sh, b);
         if (!dev_in && sf != s) check_hip(hipStreamWaitEvent(sf, h2d[(int)(b & 1)], 0), "hipStreamWaitEvent");
-        check_sdr(sdr_frontend(ctx, src, stride, sf), "sdr_frontend");
+        if (sh->tuned) check_sdr(sdr_frontend_tuned(ctx, src, stride, sf), "sdr_frontend_tuned");
+        else check_sdr(sdr_frontend(ctx, src, stride, sf), "sdr_frontend");
         if (!dev_in) check_hip(hipEventRecord(fe_done[(int)(b & 1)], sf), "hipEventRecord");
         FmBatch* fb = sh->q.acquire();
         for (auto& e : fb->released) check_hip(hipStreamWaitEvent(sf, e, 0), "hipStreamWaitEvent");
@@ -717,13 +722,26 @@ long long regular_file_blocks(const char* path, size_t block_bytes) {
     return (long long)((size_t)sb.st_size / block_bytes);
 }
 
-}  // namespace
+// the tuning's bounds (sdr_tuner_set's), checked before anything starts
+bool tuning_valid(const sdr_multi_opts* o, const sdr_multi_tuning* t) {
+    int N = 0;
+    if (sdr_tuner_table(o->mode, nullptr, 0, &N) != SDR_OK) return false;
+    if (t->nsrc < 1 || t->nsrc > o->nch || !t->src || !t->khz) return false;
+    for (int c = 0; c < o->nch; c++)
+        if (t->src[c] < 0 || t->src[c] >= t->nsrc || 2 * (long long)t->khz[c] <= -(long long)N ||
+            2 * (long long)t->khz[c] > N)
+            return false;
+    return true;
+}
 
-extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats) {
+int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_multi_stats* stats) {
     if (!opts || opts->nch <= 0 || (!opts->in_path && (!opts->d_iq || opts->nblocks <= 0)))
         return SDR_E_INVALID;
+    if (tune && !tuning_valid(opts, tune)) return SDR_E_INVALID;
     Shared sh;
     sh.o = *opts;
+    sh.tuned = tune != nullptr;
+    sh.rows = tune ? tune->nsrc : opts->nch;
     const sdr_multi_opts& o = sh.o;
     check_hip(hipSetDevice(o.device), "hipSetDevice");
     // SDR_MULTI_TRACE=1: the set-up and tear-down phases' host times on stderr
@@ -738,13 +756,18 @@ extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats)
     sh.ctx[1] = ctx_get(o.device, o.nch, o.mode, 0, o.flags);
     sh.ctx[2] = ctx_get(o.device, o.nch, o.mode, 1, o.flags);
     mark("contexts");
+    // pooled contexts keep their tuning over sdr_ctx_reset: set it on every context of a tuned run,
+    // clear it on those of an untuned one
+    for (sdr_ctx* c : sh.ctx)
+        check_sdr(tune ? sdr_tuner_set(c, tune->nsrc, tune->src, tune->khz, nullptr) : sdr_tuner_set(c, 0, nullptr, nullptr, nullptr),
+                  "sdr_tuner_set");
     check_sdr(sdr_ctx_info(sh.ctx[0], &sh.info), "sdr_ctx_info");
     const size_t row = 2 * (size_t)sh.info.block_iq;
     if (!o.in_path && o.row_stride < row) {
         for (sdr_ctx* c : sh.ctx) ctx_put(c);
         return SDR_E_INVALID;
     }
-    sh.nblocks_known = o.in_path ? regular_file_blocks(o.in_path, row * o.nch) : o.nblocks;
+    sh.nblocks_known = o.in_path ? regular_file_blocks(o.in_path, row * (size_t)sh.rows) : o.nblocks;
     // streams: the PLLs on [0, pll_cus) (halves), everything else on the rest
     const int half = o.pll_cus / 2;
     if (half > 0) {
@@ -869,4 +892,12 @@ extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats)
     mark("torn down");
     if (stats) *stats = st;
     return SDR_OK;
+}
+
+}  // namespace
+
+extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats) { return multi_run(opts, nullptr, stats); }
+
+extern "C" int sdr_multi_run_tuned(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_multi_stats* stats) {
+    return multi_run(opts, tune, stats);
 }
