@@ -12,7 +12,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-g
             -mllvm -pragma-unroll-threshold=1000000 \
             -Wall -Iinclude
 LIB      := $(PKG)/libsdr_amd.so
-SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_taps.cpp
+SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_scan.hip \
+            $(PKG)/csrc/sdr_taps.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
 HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h
 
@@ -21,9 +22,9 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -pthread -D__HIP_PLATFORM_AMD__ 
              -Iinclude -Iinclude/dropin -I$(PKG)/host
 HOSTLIB   := $(PKG)/libsdr_host.so
 HOSTSRCS  := $(PKG)/host/dropin_primitives.cpp $(PKG)/host/dropin_stages.cpp $(PKG)/host/rds_frame.cpp \
-             $(PKG)/host/sdr_multi_engine.cpp
+             $(PKG)/host/sdr_multi_engine.cpp $(PKG)/host/sdr_scan_run.cpp
 HOSTHDRS  := $(wildcard include/dropin/*.h) $(PKG)/host/hip_util.h include/sdr_amd.h include/sdr_multi.h \
-             include/sdr_multi_tuned.h
+             include/sdr_multi_tuned.h include/sdr_scan_run.h
 CLI       := $(PKG)/bin/sdr_project
 MULTI     := $(PKG)/bin/sdr_multi
 
@@ -38,6 +39,8 @@ host: $(HOSTLIB) $(CLI) $(MULTI)
 # the lane-pair PLL step is faster scalar too (packed-f32 results cost a wait state on gfx950,
 # profiles/r03/ab_pll_split3.txt)
 build/sdr_kernels.hip.o: HIPFLAGS += -fno-slp-vectorize
+# the band scan's complex multiply-adds are four scalar v_fma_f32 with SGPR twiddles: no SLP either
+build/sdr_scan.hip.o: HIPFLAGS += -fno-slp-vectorize
 build/sdr_pll.hip.o: HIPFLAGS += -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp
 # (the lane-pair PLL step scheduled for ILP: 212.4 -> 210.4 shader cycles per step, profiles/r04/ab_sched.txt)
 
@@ -56,7 +59,7 @@ $(CLI): $(PKG)/host/sdr_project.cpp $(HOSTLIB)
 	@mkdir -p $(dir $@)
 	$(CXX) $(HOSTFLAGS) -o $@ $< -L$(PKG) -lsdr_host -Wl,-rpath,'$$ORIGIN/..'
 
-$(MULTI): $(PKG)/host/sdr_multi.cpp include/sdr_multi.h include/sdr_multi_tuned.h $(HOSTLIB)
+$(MULTI): $(PKG)/host/sdr_multi.cpp include/sdr_multi.h include/sdr_multi_tuned.h include/sdr_scan_run.h $(HOSTLIB)
 	@mkdir -p $(dir $@)
 	$(CXX) $(HOSTFLAGS) -o $@ $< -L$(PKG) -lsdr_host -lsdr_amd -L$(ROCM)/lib -lamdhip64 \
 	    -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,$(ROCM)/lib

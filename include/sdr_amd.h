@@ -177,6 +177,56 @@ int sdr_tuner_get(const sdr_ctx *ctx, int *nsrc);          /* 0: not tuned */
 /* RF_frontend loop body for a tuned context: iq [nsrc][2*block_iq]. Same parity-release wait, timing
  * hooks (sdr_frontend_timing armed after sdr_tuner_set) and block advance as sdr_frontend. */
 int sdr_frontend_tuned(sdr_ctx *ctx, const uint8_t *iq, size_t iq_stride, void *stream);
+
+/* ---- band scan (sdr_version >= 3): where the stations sit in the capture rows the tuner shares.
+ * A batched power spectrum in the manner of the reference's estimatePSD (src/fourier.cpp:
+ * non-overlapping segments, Hann window, |X|^2 per bin, average over segments) whose bins are the
+ * tuner's 1 kHz steps: N = rf_Fs / 1000 as above, and a station that sdr_tuner_set reaches with
+ * khz = +f is a peak at bin f mod N (bin k is khz = k for k <= N/2 and k - N above it).
+ * A block of a row is cut into S_b = block_iq / N (30, 36, 33, 33 for modes 0..3) consecutive
+ * segments of N samples from the block's first sample on; the rest of the block is not used,
+ * segments never straddle blocks and there is no history. Per segment, in f32:
+ *     x = (u8 - 128) / 128,  w[j] = RN32(0.5 - 0.5 cos(2 pi j / N)) (evaluated in f64),
+ *     X[k] = sum_n x[n] w[n] e^(-j 2 pi k n / N),  p[k] = re^2 + im^2
+ * (a mixed-radix DFT, N = 48 x 50, 36 x 40, 32 x 36, whose every twiddle is an entry of
+ * sdr_tuner_table), and A[row][k] += sum over the block's segments of p[k] in a fixed order: a row's
+ * result is bit-identical from run to run and whatever other rows share the batch.
+ * psd[row][k] = A / S, S the segments accumulated since the last reset; no other normalisation, no dB.
+ *
+ * host only, no GPU: */
+typedef struct sdr_scan sdr_scan;
+int sdr_scan_geometry(int mode, int *n_bins, int *segments_per_block, int *block_iq);   /* any may be NULL */
+/* the f32 Hann table: *n = N, w filled when w != NULL and max >= N */
+int sdr_scan_window(int mode, float *w, int max, int *n);
+typedef struct sdr_scan_opts {
+    int half_width_khz, step_khz, first_khz, sep_khz, guard_khz;
+    float thr_db;
+} sdr_scan_opts;
+void sdr_scan_opts_default(sdr_scan_opts *o);   /* 100, 100, 0, 150, 100, 10.0f */
+/* The stations of one spectrum row, deterministic, all arithmetic in double on the f32 input:
+ *   channel power  C[k] = sum_{d = -W..W} psd[(k + d) mod N] (added in ascending d), W = half_width_khz
+ *   floor          F = the lower median of C over all N bins (element (N - 1) / 2 of the sorted values)
+ *   candidates     every khz with -N/2 + guard <= khz <= N/2 - guard and (khz - first_khz) mod step == 0
+ *                  (with guard = 0 both -N/2 and N/2 are candidates; they name the same bin)
+ *   a candidate is a station when C > 0, C >= F 10^(thr_db / 10), and no other candidate within
+ *   |delta khz| <= sep_khz has a larger C, or an equal C at a lower khz.
+ * Output in descending C, ties in ascending khz; db = 10 log10(C / F) (HUGE_VALF when F = 0). *n is
+ * the number found even when larger than max; at most max are written. SDR_E_INVALID unless
+ * 0 <= W < N/2, step >= 1, sep >= 0, 0 <= guard <= N/2 and thr_db is finite. */
+int sdr_scan_pick(int mode, const float *psd_row /*[N]*/, const sdr_scan_opts *o, int32_t *khz, float *db, int max,
+                  int *n);
+/* device: the scanner is its own handle (no channels, no sdr_ctx); it may run on its own stream beside
+ * a running pipeline, on the same device buffer sdr_frontend_tuned reads. SDR_E_INVALID for a bad
+ * mode, nsrc < 1, a short or odd stride, or NULL pointers (nothing is enqueued then). */
+int sdr_scan_create(sdr_scan **out, int device, int mode, int nsrc);
+int sdr_scan_destroy(sdr_scan *s);
+int sdr_scan_reset(sdr_scan *s, void *stream);                        /* accumulator and S back to 0 */
+/* iq [nsrc][2*block_iq], exactly sdr_frontend_tuned's input (same stride and alignment rule; rows
+ * whose first byte is 16-byte aligned load fastest); enqueues, no sync */
+int sdr_scan_block(sdr_scan *s, const uint8_t *iq, size_t iq_stride, void *stream);
+/* psd: host [nsrc][N]; *segments = S per row (psd is all zero while S = 0); synchronises `stream` */
+int sdr_scan_psd(sdr_scan *s, float *psd, long long *segments, void *stream);
+
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */

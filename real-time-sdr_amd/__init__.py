@@ -54,6 +54,12 @@ class Info(C.Structure):
                                         "n_rds", "history")]
 
 
+class ScanOpts(C.Structure):
+    """sdr_scan_opts (include/sdr_amd.h): the picker's options."""
+    _fields_ = [(n, C.c_int) for n in ("half_width_khz", "step_khz", "first_khz", "sep_khz", "guard_khz")] + \
+               [("thr_db", C.c_float)]
+
+
 def lib() -> C.CDLL:
     """Load libsdr_amd.so (built in-tree by __graft_entry__.build() / `make`)."""
     global _lib
@@ -116,6 +122,15 @@ def lib() -> C.CDLL:
         "sdr_rds_post": ([vp, vp, sz, vp], i32),
         "sdr_ctx_buffer": ([vp, C.c_char_p, C.POINTER(vp), C.POINTER(sz), C.POINTER(i32)], i32),
         "sdr_hbm_copy": ([vp, vp, sz, vp], i32),
+        "sdr_scan_geometry": ([i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], i32),
+        "sdr_scan_window": ([i32, vp, i32, C.POINTER(i32)], i32),
+        "sdr_scan_opts_default": ([C.POINTER(ScanOpts)], None),
+        "sdr_scan_pick": ([i32, vp, C.POINTER(ScanOpts), vp, vp, i32, C.POINTER(i32)], i32),
+        "sdr_scan_create": ([C.POINTER(vp), i32, i32, i32], i32),
+        "sdr_scan_destroy": ([vp], i32),
+        "sdr_scan_reset": ([vp, vp], i32),
+        "sdr_scan_block": ([vp, vp, sz, vp], i32),
+        "sdr_scan_psd": ([vp, vp, C.POINTER(C.c_longlong), vp], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -203,6 +218,107 @@ def tuner_table(mode: int):
     if lib().sdr_tuner_table(mode, t.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) != SDR_OK:
         raise SdrError("sdr_tuner_table failed", -1)
     return t
+
+
+# ------------------------------------------------------------------ band scan (include/sdr_amd.h, sdr_scan_*)
+def scan_geometry(mode: int) -> tuple[int, int, int]:
+    """(N bins = rf_Fs / 1000, segments per block, block_iq) of a mode (host only)."""
+    n, s, b = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().sdr_scan_geometry(mode, C.byref(n), C.byref(s), C.byref(b)), "sdr_scan_geometry")
+    return n.value, s.value, b.value
+
+
+def scan_window(mode: int):
+    """The scan's f32 Hann table [N]: RN32(0.5 - 0.5 cos(2 pi j / N)) (host only)."""
+    import numpy as np
+    w = np.zeros(scan_geometry(mode)[0], np.float32)
+    n = C.c_int(0)
+    check(lib().sdr_scan_window(mode, w.ctypes.data_as(C.c_void_p), w.size, C.byref(n)), "sdr_scan_window")
+    return w
+
+
+def scan_opts(**opts) -> ScanOpts:
+    """The picker's defaults (sdr_scan_opts_default) with the given fields replaced."""
+    o = ScanOpts()
+    lib().sdr_scan_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(ScanOpts._fields_):
+            raise SdrError(f"scan_pick: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+def scan_pick(mode: int, psd_row, max=None, **opts):
+    """The stations of one spectrum row [N] (sdr_scan_pick; host only): (khz int32, db f32) in
+    descending channel power. opts: half_width_khz, step_khz, first_khz, sep_khz, guard_khz, thr_db.
+    max: write at most this many (the arrays then hold min(max, found) entries)."""
+    import numpy as np
+    N = scan_geometry(mode)[0]
+    row = np.ascontiguousarray(psd_row, np.float32)
+    if row.shape != (N,):
+        raise SdrError(f"scan_pick: psd_row must have {N} entries", -1)
+    o = scan_opts(**opts)
+    cap = N + 1 if max is None else int(max)
+    khz, db = np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+    n = C.c_int(0)
+    check(lib().sdr_scan_pick(mode, row.ctypes.data_as(C.c_void_p), C.byref(o), khz.ctypes.data_as(C.c_void_p),
+                              db.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "sdr_scan_pick")
+    k = min(n.value, cap)
+    return khz[:k], db[:k]
+
+
+class Scanner:
+    """The band scan of `nsrc` capture rows of one mode (sdr_scan_*): block(iq) per block of the rows
+    sdr_frontend_tuned reads, then psd() or stations(). Its own handle: no channels, any stream."""
+
+    def __init__(self, mode: int, nsrc: int, device: int = 0):
+        h = C.c_void_p()
+        check(lib().sdr_scan_create(C.byref(h), device, mode, nsrc), "sdr_scan_create")
+        self._h = h
+        self.mode, self.nsrc, self.device = mode, nsrc, device
+        self.n_bins, self.segments_per_block, self.block_iq = scan_geometry(mode)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sdr_scan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().sdr_scan_reset(self._h, _stream(stream)), "sdr_scan_reset")
+
+    def block(self, iq, stream=None):
+        """iq: uint8 [nsrc][2*block_iq] (device); enqueues, no sync."""
+        if iq.dim() != 2 or iq.shape[0] != self.nsrc:
+            raise SdrError(f"Scanner.block: expected [{self.nsrc}][2*block_iq] rows", -1)
+        stride = _row_stride(iq) if iq.shape[0] > 1 else int(iq.shape[1])
+        check(lib().sdr_scan_block(self._h, _ptr(iq), stride, _stream(stream)), "sdr_scan_block")
+
+    def psd(self, stream=None):
+        """(numpy f32 [nsrc][N], segments accumulated per row); synchronises the stream."""
+        import numpy as np
+        out = np.zeros((self.nsrc, self.n_bins), np.float32)
+        seg = C.c_longlong(0)
+        check(lib().sdr_scan_psd(self._h, out.ctypes.data_as(C.c_void_p), C.byref(seg), _stream(stream)),
+              "sdr_scan_psd")
+        return out, seg.value
+
+    def stations(self, stream=None, **opts):
+        """(src, khz) int32 arrays over all rows, row after row, each row in the picker's order:
+        ready for Pipeline.set_tuning."""
+        import numpy as np
+        psd, _ = self.psd(stream)
+        src, khz = [], []
+        for r in range(self.nsrc):
+            k, _db = scan_pick(self.mode, psd[r], **opts)
+            src.append(np.full(k.size, r, np.int32))
+            khz.append(k)
+        return np.concatenate(src), np.concatenate(khz)
 
 
 # ------------------------------------------------------------------ batched primitives (torch tensors)

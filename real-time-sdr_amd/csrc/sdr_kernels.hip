@@ -1708,7 +1708,7 @@ namespace {
 extern "C" {
 
 const char* sdr_last_error(void) { return sdrk::last_error(); }
-int sdr_version(void) { return 2; }   // 2: the shared-capture tuner (sdr_tuner_*, sdr_frontend_tuned)
+int sdr_version(void) { return 3; }   // 2: the shared-capture tuner (sdr_tuner_*, sdr_frontend_tuned); 3: the band scan (sdr_scan_*)
 
 int sdr_stream_create_cu_range(void** stream, int device, int first_cu, int n_cu, int exclude) {
     if (!stream) return fail(SDR_E_INVALID, "sdr_stream_create_cu_range: stream is NULL");

@@ -2,6 +2,7 @@
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
 //   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE]
+//   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //
 // Input: u8 I/Q, block after block, each block NCH rows of 2*block_iq bytes (channel after
 // channel: the [block][channel][bytes] layout of bench.py). Output: PREFIX.pcm -- per block NCH
@@ -11,7 +12,11 @@
 // CU masks. --tune FILE: shared captures (include/sdr_multi_tuned.h) -- FILE is text, one "src khz"
 // pair per line, NCH lines: channel c listens to capture row src and to the station khz kHz off its
 // centre; the input then holds max(src) + 1 rows per block instead of NCH. A summary line goes to
-// stderr.
+// stderr. --scan: the band scan (include/sdr_scan_run.h) instead of the receiver -- the first B blocks
+// (default 4) of NROWS capture rows, the --tune input layout, are scanned and the stations found are
+// written to PREFIX.stations in the --tune format; --step K: the station grid in kHz (default 100),
+// --thr DB: the threshold over the floor (default 10). `sdr_multi <n> --tune PREFIX.stations` with the
+// n the scan printed then receives them.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -21,12 +26,16 @@
 #include "sdr_amd.h"
 #include "sdr_multi.h"
 #include "sdr_multi_tuned.h"
+#include "sdr_scan_run.h"
 
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
                          "[--tune FILE]\n"
-                         "  --tune FILE: NCH lines \"src khz\"; the input holds max(src)+1 capture rows per block\n");
+                         "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
+                         "[--step K] [--thr DB]\n"
+                         "  --tune FILE: NCH lines \"src khz\"; the input holds max(src)+1 capture rows per block\n"
+                         "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n");
     std::exit(1);
 }
 }  // namespace
@@ -38,6 +47,9 @@ int main(int argc, char** argv) {
     o.pll_cus = 64;
     std::string in = "-", out = "sdr_multi", tune_path;
     if (o.nch <= 0) usage();
+    bool scan = false;
+    sdr_scan_run_opts so{};
+    sdr_scan_opts_default(&so.pick);
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--mode" && i + 1 < argc) o.mode = std::atoi(argv[++i]);
@@ -45,12 +57,34 @@ int main(int argc, char** argv) {
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else if (a == "--cus" && i + 1 < argc) o.pll_cus = std::atoi(argv[++i]);
         else if (a == "--tune" && i + 1 < argc) tune_path = argv[++i];
+        else if (a == "--scan") scan = true;
+        else if (a == "--scan-blocks" && i + 1 < argc) so.max_blocks = std::atoi(argv[++i]);
+        else if (a == "--step" && i + 1 < argc) so.pick.step_khz = std::atoi(argv[++i]);
+        else if (a == "--thr" && i + 1 < argc) so.pick.thr_db = (float)std::atof(argv[++i]);
         else if (a == "--fast") o.flags |= SDR_FLAG_FAST_FRONTEND;
         else usage();
     }
     if (const char* dev = std::getenv("SDR_DEVICE")) o.device = std::atoi(dev);
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();
+    if (scan) {
+        if (!tune_path.empty()) usage();   // a scan writes a tuning, it does not take one
+        const std::string list = out + ".stations";
+        so.nrows = o.nch;
+        so.mode = o.mode;
+        so.device = o.device;
+        so.in_path = o.in_path;
+        so.out_path = list.c_str();
+        sdr_scan_run_stats ss{};
+        const int rc = sdr_scan_run(&so, &ss);
+        if (rc != SDR_OK) {
+            std::fprintf(stderr, "sdr_multi: %d %s\n", rc, ss.error);
+            return 1;
+        }
+        std::fprintf(stderr, "sdr_multi: scan: %d stations in %d rows (%lld segments per row)\n", ss.stations, so.nrows,
+                     ss.segments);
+        return 0;
+    }
     sdr_multi_stats st{};
     std::vector<int32_t> src, khz;
     sdr_multi_tuning tune{};
