@@ -427,8 +427,9 @@ __device__ __forceinline__ void pll_run(const PllJob& jb, int n, int ch, const d
 //   q = g * f_own               A: eQ0 c                          B: eI0 s
 //   Y = q + q_partner           eI0 s + eQ0 c on both lanes (the same two f64 products, one sum)
 // (pll.cpp:36-39 in the reduced frame, pll_math.h phase_detect2; xs = -x comes from the producer:
-// the sign of eQ0 cannot otherwise enter one lane only). e, the loop filter, t, the reduction and
-// the proof accumulators are identical on both lanes; the e bracket is proven half on each lane
+// the sign of eQ0 cannot otherwise enter one lane only). e, t, the reduction and the proof
+// accumulators are identical on both lanes; the loop filter's two state words live one on each lane
+// (A: phaseEst, B: integrator; pll_step_split); the e bracket is proven half on each lane
 // (A: RN32(ed - eps) = e, B: RN32(ed + eps) = e) and each lane proves its own f32 rounding tie, so
 // a chunk is accepted only when both lanes of the pair accept it. A redo runs the full checked
 // step (pll_step<true>) on both lanes of the pair with the exchanged values.
@@ -436,7 +437,7 @@ __device__ __forceinline__ void pll_run(const PllJob& jb, int n, int ch, const d
 struct SplitRegs {
     double f;        // A: cos r, B: sin r (f64)
     float fb;        // RN32(f): A: fI0, B: fQ0 (reduced frame)
-    f32x2 ip;        // {integrator, phaseEst}
+    float s;         // the loop filter's state word this lane owns: A: phaseEst, B: integrator
     double toff;
     double mr;       // -r
     uint32_t nq1, b; // 1 - q, [r < 0]
@@ -446,12 +447,16 @@ struct SplitLane {
     double c0, c1, c2, c3, c4, c5;   // P(z) = c0 + c1 z + ... + c5 z^5
     double k1, k0;                   // u = k1 r + k0
     double eps;                      // the end of the e bracket this lane proves
+    float K;                         // loop-filter gain of this lane's state word: A: Kp, B: Ki
+    float smax;                      // its range bound: A: |phaseEst| < 2^28, B: |integrator| < 2^20
     bool a;                          // even lane: cos
 };
 
-__device__ __forceinline__ SplitLane split_lane() {
+__device__ __forceinline__ SplitLane split_lane(float Kp, float Ki) {
     SplitLane L;
     L.a = (threadIdx.x & 1) == 0;
+    L.K = L.a ? Kp : Ki;
+    L.smax = L.a ? 0x1p28f : 0x1p20f;
     if (L.a) {   // cos r = 1 + z (-1/2 + C1 z + ... + C5 z^5) (pll_math.h, refitted)
         L.c0 = -0.5; L.c1 = pllm::C1; L.c2 = pllm::C2; L.c3 = pllm::C3; L.c4 = pllm::C4; L.c5 = pllm::C5;
         L.k1 = 0.0; L.k0 = 1.0; L.eps = -pllm::EPS_ABS_E2;
@@ -483,7 +488,8 @@ __device__ __forceinline__ PllRegs split_to_full(const SplitRegs& s, bool a) {
     r.s = a ? fo : s.f;
     r.fbI = a ? s.fb : fbo;
     r.fbQ = a ? fbo : s.fb;
-    r.ip = s.ip;
+    const float so = pair_swap(s.s);
+    r.ip = a ? f32x2{so, s.s} : f32x2{s.s, so};
     r.toff = s.toff;
     r.mr = s.mr;
     r.nq1 = s.nq1;
@@ -495,7 +501,7 @@ __device__ __forceinline__ SplitRegs full_to_split(const PllRegs& r, bool a) {
     SplitRegs s;
     s.f = a ? r.c : r.s;
     s.fb = a ? r.fbI : r.fbQ;
-    s.ip = r.ip;
+    s.s = a ? r.ip.y : r.ip.x;
     s.toff = r.toff;
     s.mr = r.mr;
     s.nq1 = r.nq1;
@@ -504,31 +510,44 @@ __device__ __forceinline__ SplitRegs full_to_split(const PllRegs& r, bool a) {
 }
 
 template <bool TAB>
-__device__ __forceinline__ void pll_step_split(SplitRegs& r, float xs, double rx, float Kp, float Ki, double w,
-                                               double wt, float& t_out, PllProof& pf, const SplitLane& L) {
+__device__ __forceinline__ void pll_step_split(SplitRegs& r, float xs, double rx, double w, double wt, float& t_out,
+                                               PllProof& pf, const SplitLane& L) {
     // pll.cpp:36-39 across the pair (see above)
     const float g = xs * pair_swap(r.fb);
     const double q = (double)g * r.f;
     const double base = pllm::base_angle_n(pllm::lo_word(rx), r.nq1, r.b, r.mr);
     // (ed = base + rx qA + rx qB, own product first, is one dependent level shorter but needs both
-    // bracket ends per lane: 2 instructions more, slower, profiles/r03/ab_pll_split.txt)
+    // bracket ends per lane: 2 instructions more, slower, profiles/r03/ab_pll_split.txt; again on
+    // the lane-specialised loop filter: 205.3 -> 219.0 cycles per step, profiles/r07/ab_pll_pair_lf.txt)
     const double Y = q + pair_swap(q);
     const double ed = pllm::fma_(Y, rx, base);
     const float e = (float)ed;                                     // = RN32(atan2) when proven
-    pf.split = or_xor(pf.split, __builtin_bit_cast(uint32_t, (float)(ed + L.eps)), __builtin_bit_cast(uint32_t, e));
     pf.emaxf = fmaxf(pf.emaxf, __builtin_fabsf(e));               // f32: two steps per v_max3_f32
-    {   // pll.cpp:41-42 (scalar f32, this unit is built without SLP: profiles/r03/ab_pll_split3.txt)
-        const float ki_e = Ki * e, kp_e = Kp * e;
-        const float integ = r.ip.x + ki_e;
-        r.ip.y = (r.ip.y + kp_e) + integ;
-        r.ip.x = integ;
+    // pll.cpp:41-42, one state word per lane: the two products and the two first sums are the same
+    // two opcodes, so each lane issues them once for its own word,
+    //   s1 = s + RN(K e)        A: RN(phaseEst + Kp e)    B: RN(integrator + Ki e) = integrator'
+    // and phaseEst' = RN(s1_A + s1_B) is one add with the partner's s1 as a DPP source (the f32 add
+    // commutes, so both lanes get the reference's bits). A keeps phaseEst', B keeps s1: 4 VALU for
+    // the reference's 5, every rounding the reference's, no special case. (The conversion below has
+    // no DPP form -- the f64 pipe's DPP is row_newbcast only -- so both lanes need phaseEst' in a
+    // register of their own: the select cannot be folded into a multiply-add by a per-lane 1 / 0.)
+    float s1 = r.s + L.K * e;
+    {   // this lane's end of the e bracket, ordered behind s1 (an empty asm ties the two): its add and
+        // conversion then issue between s1 and the DPP read of s1, which needs two wait states after
+        // the write -- left to itself the scheduler puts them before s1 and pads 5 of 16 steps with
+        // s_nop 1 on the dependent chain (206.2 against 205.3 cycles per step, profiles/r07/ab_pll_pair_lf.txt)
+        double edl = ed;
+        asm("" : "+v"(edl), "+v"(s1));
+        pf.split = or_xor(pf.split, __builtin_bit_cast(uint32_t, (float)(edl + L.eps)), __builtin_bit_cast(uint32_t, e));
     }
+    const float ph = s1 + pair_swap(s1);
+    r.s = L.a ? ph : s1;
     float t;
     if (TAB) {
-        t = (float)(wt + (double)r.ip.y);                         // pll.cpp:47
+        t = (float)(wt + (double)ph);                             // pll.cpp:47
     } else {
         r.toff += 1.0;                                             // pll.cpp:46
-        t = (float)(w * r.toff + (double)r.ip.y);
+        t = (float)(w * r.toff + (double)ph);
     }
     // reduction (pll_math.h sincos_rn) and this lane's kernel
     const double x = (double)t;
@@ -543,7 +562,8 @@ __device__ __forceinline__ void pll_step_split(SplitRegs& r, float xs, double rx
     // Horner: one instruction fewer than Estrin (no z^2), two dependent levels more; faster than
     // Estrin and than a two-level form (profiles/r03/ab_pll_split3.txt)
     // (Estrin, two dependent levels shorter for two multiplies more, measured again in round 5:
-    // 212 -> 224 cycles per step, with or without s_setprio; profiles/r05/ab_pll_est.txt)
+    // 212 -> 224 cycles per step, with or without s_setprio; profiles/r05/ab_pll_est.txt; and in
+    // round 7 on the lane-specialised loop filter: 205.3 -> 216.2, profiles/r07/ab_pll_pair_lf.txt)
     double P = pllm::fma_(z, L.c5, L.c4);
     P = pllm::fma_(z, P, L.c3);
     P = pllm::fma_(z, P, L.c2);
@@ -602,7 +622,6 @@ __device__ __forceinline__ void gate_wait(InGate& g, int i_end) {
 template <bool VEC, bool TAB, bool GATE = false>
 __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, const double* __restrict__ wtab,
                                               InGate* gate = nullptr) {
-    const SplitLane L = split_lane();
     const size_t in_stride = jb.in_stride, t_stride = jb.t_stride, out_stride = jb.out_stride;
     sdr_pll_state* __restrict__ st = jb.st;
     const float freq = jb.freq, Fs = jb.Fs, normBandwidth = jb.bw;
@@ -610,6 +629,7 @@ __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, c
     const float Ci = 3.555;
     const float Kp = normBandwidth * Cp;
     const float Ki = normBandwidth * normBandwidth * Ci;
+    const SplitLane L = split_lane(Kp, Ki);
     const double w = 2 * 3.14159265358979323846 * (freq / Fs);
     const sdr_pll_state s0 = st[ch];
     const float* xpos = jb.in + (size_t)ch * in_stride;
@@ -665,16 +685,15 @@ __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, c
             float tv[C];
 #pragma unroll
             for (int j = 0; j < C; j++)
-                pll_step_split<TAB>(r, xb[u][j], rb[u][j], Kp, Ki, w, TAB ? wv[j] : 0.0, tv[j], pf, L);
+                pll_step_split<TAB>(r, xb[u][j], rb[u][j], w, TAB ? wv[j] : 0.0, tv[j], pf, L);
             // this lane's proof: its half of the e bracket, the e range, its own rounding ties, and
             // the state range (a NaN from an invalid input fails it)
             const bool ok = (pf.emaxf < PLL_EMAX_F) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
-                            (__builtin_fabs(r.ip.y) < 0x1p28f) & (__builtin_fabs(r.ip.x) < 0x1p20f) &
-                            (TAB || (pf.tmax < 0x1p30f));
+                            (__builtin_fabs(r.s) < L.smax) & (TAB || (pf.tmax < 0x1p30f));
 #if SDR_PLL_COUNT
             pll_count_chunk(ok);
             pll_count_reasons(!(pf.emaxf < PLL_EMAX_F), pf.split != 0u, !(pf.tie > pllm::TIE_MIN),
-                              !((__builtin_fabs(r.ip.y) < 0x1p28f) & (__builtin_fabs(r.ip.x) < 0x1p20f)));
+                              !(__builtin_fabs(r.s) < L.smax));
 #endif
             // the partner's verdict, read with every lane of the pair active (under `ok && ...` the
             // exchange would sit in a branch, and a lane reading a disabled partner keeps its own value)
@@ -768,7 +787,6 @@ template <bool TAB, bool GATE>
 __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int ch, const double* __restrict__ wtab,
                                                    InGate* gate, uint8_t* __restrict__ lbuf,
                                                    uint8_t* __restrict__ ltst) {
-    const SplitLane L = split_lane();
     const int lane = threadIdx.x & 63;
     const int chw0 = ch - (lane >> 1);                 // the wave's first channel
     const size_t t_stride = jb.t_stride, out_stride = jb.out_stride;
@@ -778,6 +796,7 @@ __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int 
     const float Ci = 3.555;
     const float Kp = normBandwidth * Cp;
     const float Ki = normBandwidth * normBandwidth * Ci;
+    const SplitLane L = split_lane(Kp, Ki);
     const double w = 2 * 3.14159265358979323846 * (freq / Fs);
     const sdr_pll_state s0 = st[ch];
     const float* xpos = jb.in + (size_t)ch * jb.in_stride;
@@ -865,10 +884,9 @@ __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int 
             float tv[C];
 #pragma unroll
             for (int j = 0; j < C; j++)
-                pll_step_split<TAB>(r, xb[j], rb[j], Kp, Ki, w, TAB ? wv[j] : 0.0, tv[j], pf, L);
+                pll_step_split<TAB>(r, xb[j], rb[j], w, TAB ? wv[j] : 0.0, tv[j], pf, L);
             const bool ok = (pf.emaxf < PLL_EMAX_F) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
-                            (__builtin_fabs(r.ip.y) < 0x1p28f) & (__builtin_fabs(r.ip.x) < 0x1p20f) &
-                            (TAB || (pf.tmax < 0x1p30f));
+                            (__builtin_fabs(r.s) < L.smax) & (TAB || (pf.tmax < 0x1p30f));
             const int ok_partner = __builtin_amdgcn_mov_dpp((int)ok, 0xB1, 0xF, 0xF, false);
             const bool pair_ok = ok & (ok_partner != 0);
             if (!pair_ok) {
