@@ -227,6 +227,86 @@ int sdr_scan_block(sdr_scan *s, const uint8_t *iq, size_t iq_stride, void *strea
 /* psd: host [nsrc][N]; *segments = S per row (psd is all zero while S = 0); synchronises `stream` */
 int sdr_scan_psd(sdr_scan *s, float *psd, long long *segments, void *stream);
 
+/* ---- reception meter (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
+ * per channel and block, what a receiver's stereo lamp and tuning indicator show, reduced on the GPU
+ * from rows the pipeline already keeps. n = block_if, x = the block's fm_demod row, x[-100..-1] the
+ * previous block's tail (zeros before block 0):
+ *   fm_sum, fm_sq, fm_peak   sum x, sum x^2, max |x| (NaN ignored)
+ *   pilot_sq                 sum pilot^2 over the 19 kHz pilot row (sdr_stereo_pre)
+ *   noise_sq                 sum y^2, y[j] = sum_{k=0..100} h_n[k] x[5j - k], j < n/5, with
+ *                            h_n = sdr_impulse_response_bpf(if_Fs, {75e3, 84e3}, 101): the discriminator's
+ *                            noise in the gap between the 67 and 92 kHz SCA sub-carriers, every fifth point
+ *   rds_sq                   sum rds_band^2 over the 57 kHz RDS band row (sdr_rds_pre)
+ *   eye_abs, eye_sq, eye_n   s_k = |rds_clean[off + k symbol_Fs]| for every index below n_rds, with
+ *                            off = cdr(symbol_Fs, rds_clean) run by the meter on every block (whatever
+ *                            sdr_rds_bits does): sum s_k, sum s_k^2 and their count
+ *   l_peak, r_peak, l_sq, r_sq   max |s| and sum s^2 of the int16 L and R samples, exact integers
+ * Numerics: every f32 product and sum is rounded on its own (no FMA), a square is fl(v v), the noise
+ * FIR adds its products in ascending k from +0 (convolveFIR, filter.cpp:106-121). A float sum over a
+ * row of length m: partial p (0 <= p < 256) adds the elements i = p (mod 256) in ascending i from +0;
+ * then P[p] = fl(P[p] + P[p + w]) for p < w, w = 128, 64, .., 1; the result is P[0]. The eye sums use
+ * 64 partials and six levels. A row is therefore bit-identical from run to run and whatever the batch.
+ * Units: the discriminator is fmDemodNoArctan, whose output is about the sine of the phase step, not
+ * the step: the readings are discriminator units and ratios of them, NOT deviation in kHz (the
+ * 7.5 kHz pilot of the synthetic multiplex reads about 1.46 kHz under the small-signal conversion
+ * if_Fs / 2 pi). */
+typedef struct sdr_meter_row {   /* 64 bytes */
+    float fm_sum, fm_sq, fm_peak, pilot_sq, noise_sq, rds_sq, eye_abs, eye_sq;
+    int32_t eye_n, flags;        /* flags: SDR_METER_ROW_* */
+    int32_t l_peak, r_peak;
+    uint64_t l_sq, r_sq;
+} sdr_meter_row;
+/* row flags: that part of the row holds a reading, written by its call on that call's current block;
+ * set by the first such call after create / sdr_meter_reset */
+#define SDR_METER_ROW_AUDIO 0x1  /* sdr_meter_audio: fm_*, pilot_sq, noise_sq, l_*, r_* */
+#define SDR_METER_ROW_RDS 0x2    /* sdr_meter_rds: rds_sq, eye_* */
+typedef struct sdr_meter sdr_meter;
+/* host only, no GPU: the noise band-pass of a mode; *n = 101, h filled when h != NULL and max >= 101 */
+int sdr_meter_taps(int mode, float *h, int max, int *n);
+typedef struct sdr_meter_opts {
+    float pilot_nr_min, rds_nr_min, offtune_min;
+    int silence_peak;
+} sdr_meter_opts;
+void sdr_meter_opts_default(sdr_meter_opts *o);   /* 1.0f, 4.0f, 0.25f, 64 */
+#define SDR_METER_STEREO 0x1     /* pilot_nr >= pilot_nr_min */
+#define SDR_METER_RDS 0x2        /* rds_nr >= rds_nr_min */
+#define SDR_METER_OFFTUNE 0x4    /* |offset| >= offtune_min */
+#define SDR_METER_DEAD_AIR 0x8   /* the audio part is written and l_peak, r_peak <= silence_peak */
+typedef struct sdr_meter_state {
+    double offset, level_db, pilot_nr, rds_nr, eye_db;
+    int flags;                   /* SDR_METER_STEREO | ... */
+} sdr_meter_state;
+/* One row's readings, in double on the row's values (n = block_if of the mode):
+ *   offset = fm_sum / n,  level_db = 10 log10(fm_sq / n)
+ *   pilot_nr = (pilot_sq / n) / (noise_sq / (n / 5)),  rds_nr likewise from rds_sq
+ *   eye_db = 10 log10(m1^2 / (m2 - m1^2)),  m1 = eye_abs / eye_n,  m2 = eye_sq / eye_n
+ * A ratio with a zero numerator (or eye_n = 0) is 0, one with a zero denominator under a positive
+ * numerator is +infinity; the dB of 0 is -infinity. */
+int sdr_meter_status(int mode, const sdr_meter_row *row, const sdr_meter_opts *o, sdr_meter_state *out);
+/* device: the meter is its own handle, like the scanner; it owns the taps and rows[nch] (all zero after
+ * create and sdr_meter_reset). Both calls enqueue one kernel on `stream` and write their fields of every
+ * channel's row for `ctx`'s current block; they may use two contexts (an audio and an RDS one joined by
+ * sdr_push_fm_demod) and two streams and still fill one row.
+ *   sdr_meter_audio  fm_*, pilot_sq, noise_sq and the audio fields; needs sdr_stereo_pre (or sdr_pre)
+ *                    of the block. lr is the row sdr_stereo / sdr_stereo_post wrote for it, ordered by
+ *                    the caller; NULL leaves the audio fields 0.
+ *   sdr_meter_rds    rds_sq and the eye fields; needs sdr_rds_pre and sdr_rds_post (or sdr_rds_dsp) of
+ *                    the block, on this stream or ordered before it (rds_clean is not a parity buffer:
+ *                    the rule of sdr_rds_bits).
+ * The meter is a reader in the parity-release protocol (fm, pilot and rds_band belong to the block's
+ * parity): the producers of the block two later wait for it as for sdr_stereo_post; a context no meter
+ * call ran on waits for nothing new. SDR_E_INVALID, nothing enqueued: NULL handles, a context of
+ * another nch, mode or device, a short lr_stride, a stage that has not run for the current block,
+ * rds_on = 0 in sdr_meter_rds. SDR_E_TIMEOUT as every stage call. */
+int sdr_meter_create(sdr_meter **out, int device, int nch, int mode);
+int sdr_meter_destroy(sdr_meter *m);
+int sdr_meter_reset(sdr_meter *m, void *stream);
+int sdr_meter_audio(sdr_meter *m, sdr_ctx *ctx, const int16_t *lr, size_t lr_stride, void *stream);
+int sdr_meter_rds(sdr_meter *m, sdr_ctx *ctx, void *stream);
+/* host_rows [nch]; synchronises `stream` */
+int sdr_meter_read(sdr_meter *m, sdr_meter_row *host_rows, void *stream);
+int sdr_meter_rows(sdr_meter *m, const sdr_meter_row **dev);   /* the device rows [nch] */
+
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */

@@ -60,6 +60,28 @@ class ScanOpts(C.Structure):
                [("thr_db", C.c_float)]
 
 
+class MeterRow(C.Structure):
+    """sdr_meter_row (include/sdr_amd.h): one channel's readings of one block, 64 bytes."""
+    _fields_ = [(n, C.c_float) for n in ("fm_sum", "fm_sq", "fm_peak", "pilot_sq", "noise_sq", "rds_sq", "eye_abs",
+                                          "eye_sq")] + \
+               [(n, C.c_int32) for n in ("eye_n", "flags", "l_peak", "r_peak")] + \
+               [(n, C.c_uint64) for n in ("l_sq", "r_sq")]
+
+
+class MeterOpts(C.Structure):
+    """sdr_meter_opts: the thresholds of meter_status."""
+    _fields_ = [(n, C.c_float) for n in ("pilot_nr_min", "rds_nr_min", "offtune_min")] + [("silence_peak", C.c_int)]
+
+
+class MeterState(C.Structure):
+    """sdr_meter_state: what sdr_meter_status makes of a row."""
+    _fields_ = [(n, C.c_double) for n in ("offset", "level_db", "pilot_nr", "rds_nr", "eye_db")] + [("flags", C.c_int)]
+
+
+METER_ROW_AUDIO, METER_ROW_RDS = 0x1, 0x2                                   # MeterRow.flags
+METER_STEREO, METER_RDS, METER_OFFTUNE, METER_DEAD_AIR = 0x1, 0x2, 0x4, 0x8   # MeterState.flags
+
+
 def lib() -> C.CDLL:
     """Load libsdr_amd.so (built in-tree by __graft_entry__.build() / `make`)."""
     global _lib
@@ -131,6 +153,16 @@ def lib() -> C.CDLL:
         "sdr_scan_reset": ([vp, vp], i32),
         "sdr_scan_block": ([vp, vp, sz, vp], i32),
         "sdr_scan_psd": ([vp, vp, C.POINTER(C.c_longlong), vp], i32),
+        "sdr_meter_taps": ([i32, vp, i32, C.POINTER(i32)], i32),
+        "sdr_meter_opts_default": ([C.POINTER(MeterOpts)], None),
+        "sdr_meter_status": ([i32, C.POINTER(MeterRow), C.POINTER(MeterOpts), C.POINTER(MeterState)], i32),
+        "sdr_meter_create": ([C.POINTER(vp), i32, i32, i32], i32),
+        "sdr_meter_destroy": ([vp], i32),
+        "sdr_meter_reset": ([vp, vp], i32),
+        "sdr_meter_audio": ([vp, vp, vp, sz, vp], i32),
+        "sdr_meter_rds": ([vp, vp, vp], i32),
+        "sdr_meter_read": ([vp, vp, vp], i32),
+        "sdr_meter_rows": ([vp, C.POINTER(vp)], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -319,6 +351,119 @@ class Scanner:
             src.append(np.full(k.size, r, np.int32))
             khz.append(k)
         return np.concatenate(src), np.concatenate(khz)
+
+
+# ------------------------------------------------------------------ reception meter (include/sdr_amd.h, sdr_meter_*)
+def meter_row_dtype():
+    """numpy dtype of sdr_meter_row (64 bytes)."""
+    import numpy as np
+    return np.dtype(MeterRow)
+
+
+def meter_taps(mode: int):
+    """The meter's noise band-pass [101]: impulse_response_bpf(if_Fs, 75e3, 84e3, 101) (host only)."""
+    import numpy as np
+    n = C.c_int(0)
+    check(lib().sdr_meter_taps(mode, None, 0, C.byref(n)), "sdr_meter_taps")
+    h = np.zeros(n.value, np.float32)
+    check(lib().sdr_meter_taps(mode, h.ctypes.data_as(C.c_void_p), h.size, C.byref(n)), "sdr_meter_taps")
+    return h
+
+
+def meter_opts(**opts) -> MeterOpts:
+    """The status thresholds' defaults (sdr_meter_opts_default) with the given fields replaced."""
+    o = MeterOpts()
+    lib().sdr_meter_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(MeterOpts._fields_):
+            raise SdrError(f"meter_status: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+def meter_status(mode: int, rows, **opts):
+    """sdr_meter_status of every row (host only): rows is a MeterRow or a numpy array of
+    meter_row_dtype(); returns a numpy structured array (offset, level_db, pilot_nr, rds_nr, eye_db,
+    flags) of the same shape. The readings are discriminator units and ratios, not kHz of deviation.
+    opts: pilot_nr_min, rds_nr_min, offtune_min, silence_peak."""
+    import numpy as np
+    o = meter_opts(**opts)
+    if isinstance(rows, MeterRow):
+        rows = np.frombuffer(bytes(rows), dtype=meter_row_dtype())[0]
+    rows = np.asarray(rows, dtype=meter_row_dtype())
+    flat = np.ascontiguousarray(rows).reshape(-1)
+    out = np.zeros(flat.shape, np.dtype(MeterState))
+    st = MeterState()
+    for i in range(flat.size):
+        row = MeterRow.from_buffer_copy(flat[i].tobytes())
+        check(lib().sdr_meter_status(mode, C.byref(row), C.byref(o), C.byref(st)), "sdr_meter_status")
+        out[i] = (st.offset, st.level_db, st.pilot_nr, st.rds_nr, st.eye_db, st.flags)
+    return out.reshape(rows.shape)
+
+
+class Meter:
+    """The reception meter of `nch` channels of one mode (sdr_meter_*): per block audio(pipe, lr) after
+    the block's stereo stage and rds(pipe) after its RDS stage -- on one Pipeline or on two joined by
+    push_fm_demod -- then rows() or status(). Its own handle; the rows stay on the device."""
+
+    def __init__(self, nch: int, mode: int = 0, device: int = 0):
+        h = C.c_void_p()
+        check(lib().sdr_meter_create(C.byref(h), device, nch, mode), "sdr_meter_create")
+        self._h = h
+        self.nch, self.mode, self.device = nch, mode, device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sdr_meter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().sdr_meter_reset(self._h, _stream(stream)), "sdr_meter_reset")
+
+    def audio(self, pipe: "Pipeline", lr=None, stream=None):
+        """The fm, pilot, noise and audio fields of pipe's current block; lr: the int16 [nch][2*n_audio]
+        tensor stereo() / stereo_post() wrote (None: the audio fields stay 0). Enqueues, no sync."""
+        stride = 0 if lr is None else (_row_stride(lr) if lr.shape[0] > 1 else int(lr.shape[1]))
+        check(lib().sdr_meter_audio(self._h, pipe._h, _ptr(lr), stride, _stream(stream)), "sdr_meter_audio")
+
+    def rds(self, pipe: "Pipeline", stream=None):
+        """rds_sq and the eye fields of pipe's current block (after rds() / rds_post())."""
+        check(lib().sdr_meter_rds(self._h, pipe._h, _stream(stream)), "sdr_meter_rds")
+
+    def rows(self, stream=None):
+        """numpy structured array [nch] of meter_row_dtype(); synchronises the stream."""
+        import numpy as np
+        out = np.zeros(self.nch, meter_row_dtype())
+        check(lib().sdr_meter_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_meter_read")
+        return out
+
+    def rows_into(self, out, stream=None):
+        """The rows copied on the device into `out` (a contiguous uint8 tensor of nch * 64 bytes) in
+        `stream`'s order, without synchronising: for schedules that keep every block's rows."""
+        nbytes = self.nch * C.sizeof(MeterRow)
+        if out.numel() * out.element_size() != nbytes or not out.is_contiguous():
+            raise SdrError(f"Meter.rows_into: expected a contiguous tensor of {nbytes} bytes", -1)
+        rc = _hip().hipMemcpyAsync(C.c_void_p(out.data_ptr()), C.c_void_p(self.rows_ptr()), C.c_size_t(nbytes),
+                                   C.c_int(3), C.c_void_p(_stream(stream)))
+        if rc != 0:
+            raise SdrError(f"hipMemcpyAsync failed ({rc})")
+        return out
+
+    def rows_ptr(self) -> int:
+        """Device address of the rows [nch] (sdr_meter_rows)."""
+        p = C.c_void_p()
+        check(lib().sdr_meter_rows(self._h, C.byref(p)), "sdr_meter_rows")
+        return int(p.value)
+
+    def status(self, stream=None, **opts):
+        """meter_status of the current rows (synchronises the stream)."""
+        return meter_status(self.mode, self.rows(stream), **opts)
 
 
 # ------------------------------------------------------------------ batched primitives (torch tensors)
@@ -659,5 +804,6 @@ def _hip():
             raise SdrError("libamdhip64.so not found")
         _hiplib.hipMemcpy2D.restype = C.c_int
         _hiplib.hipMemcpy2DAsync.restype = C.c_int
+        _hiplib.hipMemcpyAsync.restype = C.c_int
         _hiplib.hipStreamSynchronize.restype = C.c_int
     return _hiplib

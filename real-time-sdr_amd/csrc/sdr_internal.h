@@ -3,6 +3,8 @@
 //   sdr_frontend.hip   u8 I/Q -> 101-tap FIR /D on I and Q -> discriminator   rffrontend.cpp:58-71
 //   sdr_pll.hip        PLL / NCO recurrences, persistent PLL hand-offs        pll.cpp:4-61
 //   sdr_kernels.hip    IF FIRs, resamplers, mixers, RDS bits, context and the C ABI
+//   sdr_scan.hip       band scan of the capture rows
+//   sdr_meter.hip      reception meter: per-channel readings of a block's rows
 //
 // Layout: channel-major [nch][len]. Every f32 stream that a later FIR/resampler reads with
 // look-back is kept "extended": [2 parities][nch][HIST + len], the first HIST samples being the
@@ -179,6 +181,13 @@ constexpr uint32_t PLL_SUB_SCALE = 8;
 constexpr uint32_t PLL_DONE_RING = 16; // waves stay within a few blocks of each other
 constexpr int PLL_WORDS = PLL_WORDS_DONE + (int)PLL_DONE_RING;
 
+// ---- sdr_kernels.hip, for sdr_meter.hip
+int mode_info(sdr_info* in, int nch, int mode, int rds_on);   // the mode table (sdr_ctx_info of such a context)
+int ctx_check_failed(const sdr_ctx* c, const char* what);     // SDR_E_TIMEOUT after a release timeout
+// the meter read the current block's parity buffers on s: part 0 fm and pilot (sdr_meter_audio),
+// part 1 rds_band (sdr_meter_rds); records the release (sdr_ctx rel_words)
+int meter_release(sdr_ctx* c, int part, hipStream_t s);
+
 }  // namespace sdrk
 
 // ============================================================================================
@@ -248,8 +257,11 @@ struct sdr_ctx {
     // parity release (sdr_kernels.hip release_record / release_wait): rel_words[p][slot] counts the
     // blocks of parity p read by slot 0 sdr_mono (fm), 1 sdr_stereo_post (fm, band, t_st, carrier),
     // 2 sdr_rds_post's mixer (rband, t_rds, ipll), stored on the reader's stream (rel_stream) after
-    // its kernels; the producers of the block two later wait for the count on their own streams
-    static constexpr int REL_SLOTS = 3;
+    // its kernels; the producers of the block two later wait for the count on their own streams.
+    // Slots 3 and 4 are the reception meter's two calls (sdr_meter.hip), which may run on two streams:
+    // 3 sdr_meter_audio (fm, pilot), 4 sdr_meter_rds (rband); their counts stay 0, and nothing waits
+    // for them, on a context no meter call ran on
+    static constexpr int REL_SLOTS = 5;
     uint32_t* rel_words = nullptr;                      // [2][REL_SLOTS] counters
     uint32_t rel_seq[2][REL_SLOTS] = {};
     hipStream_t rel_stream[2][REL_SLOTS] = {};

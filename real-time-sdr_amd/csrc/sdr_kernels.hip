@@ -1099,13 +1099,16 @@ __global__ __launch_bounds__(BLK) void k_mix(const float* __restrict__ a, size_t
 // stage then poisons its block: a reader that runs after the producer's overwrite would read the
 // next block's data) and its host-mapped mirror (the next stage call returns SDR_E_TIMEOUT) before it
 // lets the stream go on, so no reader can start after the overwrite without seeing the word.
-__global__ void k_rel_wait(const uint32_t* w, uint32_t want0, uint32_t want1, uint32_t want2, unsigned mask,
-                           uint32_t* fail, uint32_t* fail_host) {
+struct RelWant {
+    uint32_t v[sdr_ctx::REL_SLOTS];
+};
+__global__ void k_rel_wait(const uint32_t* w, const RelWant wants, unsigned mask, uint32_t* fail, uint32_t* fail_host) {
     if (threadIdx.x != 0) return;
-    const uint32_t want[3] = {want0, want1, want2};
+    const uint32_t* want = wants.v;
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     bool expired = false;
-    for (int k = 0; k < 3 && !expired; k++) {
+#pragma unroll
+    for (int k = 0; k < sdr_ctx::REL_SLOTS && !expired; k++) {
         if (!(mask & (1u << k))) continue;
         while ((int32_t)(__hip_atomic_load(w + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want[k]) < 0) {
             __builtin_amdgcn_s_sleep(4);
@@ -2073,9 +2076,14 @@ FrontendArgs frontend_args(const sdr_ctx* c, const uint8_t* iq, size_t iq_stride
 // not HIP events: a cross-stream event wait between the CU-masked streams started the waiting
 // stream 60-200 us after the event's work had completed (profiles/r04/release/), a kernel poll
 // within a few us.
-constexpr unsigned REL_MONO = 1u, REL_STEREO = 2u, REL_RDS = 4u;
+// The reception meter's calls are readers too (sdr_meter.hip): REL_METER_A sdr_meter_audio (fm, pilot),
+// REL_METER_R sdr_meter_rds (rband) -- a slot each, because the two may run on different streams and a
+// slot's word is stored, not added to. On a context no meter call ran on their counts stay 0 and
+// release_wait skips them: such a context enqueues what it always did.
+constexpr unsigned REL_MONO = 1u, REL_STEREO = 2u, REL_RDS = 4u, REL_METER_A = 8u, REL_METER_R = 16u;
+constexpr unsigned REL_ALL = REL_MONO | REL_STEREO | REL_RDS | REL_METER_A | REL_METER_R;
 int release_record(sdr_ctx* c, unsigned slot, hipStream_t s) {
-    const int p = c->parity, k = slot == REL_MONO ? 0 : slot == REL_STEREO ? 1 : 2;
+    const int p = c->parity, k = __builtin_ctz(slot);
     c->rel_seq[p][k]++;
     c->rel_stream[p][k] = s;
     return launch_flag_store(c->rel_words + p * sdr_ctx::REL_SLOTS + k, c->rel_seq[p][k], s);
@@ -2092,8 +2100,10 @@ int release_wait(sdr_ctx* c, int p, unsigned slots, hipStream_t s) {
         c->rel_waited_on[p][k] = s;
     }
     if (!mask) return SDR_OK;
-    hipLaunchKernelGGL(k_rel_wait, dim3(1), dim3(64), 0, s, c->rel_words + p * sdr_ctx::REL_SLOTS, c->rel_seq[p][0],
-                       c->rel_seq[p][1], c->rel_seq[p][2], mask, c->fail_words, c->fail_host_dev);
+    RelWant wants;
+    for (int k = 0; k < sdr_ctx::REL_SLOTS; k++) wants.v[k] = c->rel_seq[p][k];
+    hipLaunchKernelGGL(k_rel_wait, dim3(1), dim3(64), 0, s, c->rel_words + p * sdr_ctx::REL_SLOTS, wants, mask,
+                       c->fail_words, c->fail_host_dev);
     LAUNCH_CHECK();
     return SDR_OK;
 }
@@ -2137,6 +2147,12 @@ int check_iq(const sdr_ctx* c, const uint8_t* iq, size_t iq_stride) {
     return SDR_OK;
 }
 }  // namespace
+// what sdr_meter.hip needs of the above (sdr_internal.h)
+namespace sdrk {
+int mode_info(sdr_info* in, int nch, int mode, int rds_on) { return fill_info(in, nch, mode, rds_on); }
+int ctx_check_failed(const sdr_ctx* c, const char* what) { return check_failed(c, what); }
+int meter_release(sdr_ctx* c, int part, hipStream_t s) { return release_record(c, part ? REL_METER_R : REL_METER_A, s); }
+}  // namespace sdrk
 }  // extern "C++"
 
 int sdr_frontend(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* stream) {
@@ -2148,7 +2164,7 @@ int sdr_frontend(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* stream) 
     // fm of parity p, and the pre stages' buffers too (one wait kernel: sdr_pre on this stream then
     // has nothing left to wait for; waiting for the RDS mixer only before the pre stages measured the
     // same, profiles/r04/release/)
-    if (const int rw = release_wait(c, p, REL_MONO | REL_STEREO | REL_RDS, S(stream))) return rw;
+    if (const int rw = release_wait(c, p, REL_ALL, S(stream))) return rw;
     FrontendArgs a = frontend_args(c, iq, iq_stride, p);
     const bool timed = c->fe_time_n < c->fe_time_cap;
     if (timed && c->fe_use_stamps) {   // sdr_frontend_timing: the kernel's own workgroup stamps
@@ -2216,7 +2232,7 @@ int sdr_frontend_tuned(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* st
     if (const int r = check_iq(c, iq, iq_stride)) return r;
     if (c->tn_nsrc <= 0) return fail(SDR_E_INVALID, "frontend_tuned: the context is not tuned (sdr_tuner_set)");
     const int p = c->parity ^ 1;
-    if (const int rw = release_wait(c, p, REL_MONO | REL_STEREO | REL_RDS, S(stream))) return rw;
+    if (const int rw = release_wait(c, p, REL_ALL, S(stream))) return rw;
     FrontendArgs a = frontend_args(c, iq, iq_stride, p);   // (the tail rows are per source row here)
     const bool timed = c->fe_time_n < c->fe_time_cap && c->fe_use_stamps &&
                        c->fe_stamp_wgs == frontend_tuned_wgs(c->info.block_if, c->nch, c->nxcc);
@@ -2319,7 +2335,7 @@ int sdr_frontend_release_wait(sdr_ctx* c, void* stream) {
     if (const int rf_ = check_failed(c, "frontend_release_wait")) return rf_;
     // the wait the next sdr_frontend (or sdr_frontend_pre_parts) enqueues first; it then finds the
     // counts already waited for on this stream and enqueues none
-    return release_wait(c, c->parity ^ 1, REL_MONO | REL_STEREO | REL_RDS, S(stream));
+    return release_wait(c, c->parity ^ 1, REL_ALL, S(stream));
 }
 
 int sdr_get_fm_demod(sdr_ctx* c, float* fm, size_t fm_stride, void* stream) {
@@ -2415,8 +2431,8 @@ int sdr_stereo_pre(sdr_ctx* c, void* stream) {
     if (const int rf_ = check_failed(c, "stereo_pre")) return rf_;
     if (c->block < 0 || c->st_pre_done == c->block) return fail(SDR_E_INVALID, "stereo_pre: no new block");
     if (c->ntaps != FRB_T) return fail(SDR_E_INVALID, "stereo_pre: %d taps", c->ntaps);
-    // band of this parity read by the stereo post stage two blocks back
-    if (const int rw = release_wait(c, c->parity, REL_STEREO, S(stream))) return rw;
+    // band of this parity read by the stereo post stage two blocks back (pilot by the meter)
+    if (const int rw = release_wait(c, c->parity, REL_STEREO | REL_METER_A, S(stream))) return rw;
     // pilot BPF (stereo.cpp:74) + band BPF (:80) from one staged window of fm_demod
     const int r = fir_rb<2, false>(c, c->fm_cur(), c->fm_stride, c->info.block_if, stereo_fir(c), S(stream));
     if (r) return r;
@@ -2556,7 +2572,7 @@ int sdr_rds_pre(sdr_ctx* c, void* stream) {
     hipStream_t s = S(stream);
     const int n = c->info.block_if, p = c->parity;
     float* rband = c->rband + p * c->fm_par;
-    if (const int rw = release_wait(c, p, REL_RDS, s)) return rw;   // rband read by the RDS mixer
+    if (const int rw = release_wait(c, p, REL_RDS | REL_METER_R, s)) return rw;   // rband read by the RDS mixer (and the meter)
     // RDS band BPF (rds.cpp:105) into the extended rds_band stream
     hipLaunchKernelGGL(k_hist_copy, dim3(c->nch), dim3(HIST), 0, s, rband, c->rband + (p ^ 1) * c->fm_par,
                        c->fm_stride, n);
@@ -2598,7 +2614,7 @@ int sdr_pre(sdr_ctx* c, void* stream) {
         return fail(SDR_E_INVALID, "pre: no new block");
     if (!c->rds_on) return sdr_stereo_pre(c, stream);
     if (c->ntaps != FRB_T) return fail(SDR_E_INVALID, "pre: %d taps", c->ntaps);
-    if (const int rw = release_wait(c, c->parity, REL_STEREO | REL_RDS, S(stream))) return rw;
+    if (const int rw = release_wait(c, c->parity, REL_STEREO | REL_RDS | REL_METER_A | REL_METER_R, S(stream))) return rw;
     const int r = pre_launch(c, S(stream));
     if (r) return r;
     c->st_pre_done = c->rds_pre_done = c->block;
@@ -2842,7 +2858,7 @@ int sdr_frontend_pre_parts(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, int 
     nparts = std::min(nparts, ntiles);
     const int p = c->parity ^ 1;
     const FrontendArgs a = frontend_args(c, iq, iq_stride, p);
-    if (const int rw = release_wait(c, p, REL_MONO | REL_STEREO | REL_RDS, s)) return rw;
+    if (const int rw = release_wait(c, p, REL_ALL, s)) return rw;
     const int parity0 = c->parity;
     const long long block0 = c->block;
     c->parity = p;                 // the block's buffers (the pre-PLL FIRs read c->parity)
@@ -3270,7 +3286,7 @@ int sdr_push_fm_demod(sdr_ctx* c, const float* fm, size_t fm_stride, void* strea
     const sdr_info& in = c->info;
     const int p = c->parity ^ 1;
     float* dst = c->fm + p * c->fm_par;
-    if (const int rw = release_wait(c, p, REL_MONO | REL_STEREO, S(stream))) return rw;
+    if (const int rw = release_wait(c, p, REL_MONO | REL_STEREO | REL_METER_A, S(stream))) return rw;
     if (const int r = copy_rows(dst, c->fm_stride, fm, fm_stride, in.block_if, c->nch, c->fm + (p ^ 1) * c->fm_par,
                                 S(stream)))
         return r;

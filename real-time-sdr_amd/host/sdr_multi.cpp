@@ -1,7 +1,7 @@
 // sdr_multi.cpp -- multi-channel receiver CLI over the engine of include/sdr_multi.h (the reference
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
-//   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE]
+//   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //
 // Input: u8 I/Q, block after block, each block NCH rows of 2*block_iq bytes (channel after
@@ -16,7 +16,10 @@
 // (default 4) of NROWS capture rows, the --tune input layout, are scanned and the stations found are
 // written to PREFIX.stations in the --tune format; --step K: the station grid in kHz (default 100),
 // --thr DB: the threshold over the floor (default 10). `sdr_multi <n> --tune PREFIX.stations` with the
-// n the scan printed then receives them.
+// n the scan printed then receives them. --meter: the reception meter (include/sdr_multi_meter.h) beside the
+// receiver, with or without --tune -- PREFIX.meter (per block NCH rows of 64 bytes, sdr_meter_row) and
+// PREFIX.status (per channel the run's mean readings and its STEREO / RDS / OFFTUNE / DEAD_AIR flags);
+// the PCM and the RDS text are those of a run without it.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -25,16 +28,18 @@
 
 #include "sdr_amd.h"
 #include "sdr_multi.h"
+#include "sdr_multi_meter.h"
 #include "sdr_multi_tuned.h"
 #include "sdr_scan_run.h"
 
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
-                         "[--tune FILE]\n"
+                         "[--tune FILE] [--meter]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
                          "  --tune FILE: NCH lines \"src khz\"; the input holds max(src)+1 capture rows per block\n"
+                         "  --meter: also write PREFIX.meter (64-byte readings per channel and block) and PREFIX.status\n"
                          "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n");
     std::exit(1);
 }
@@ -47,7 +52,7 @@ int main(int argc, char** argv) {
     o.pll_cus = 64;
     std::string in = "-", out = "sdr_multi", tune_path;
     if (o.nch <= 0) usage();
-    bool scan = false;
+    bool scan = false, meter = false;
     sdr_scan_run_opts so{};
     sdr_scan_opts_default(&so.pick);
     for (int i = 2; i < argc; i++) {
@@ -58,6 +63,7 @@ int main(int argc, char** argv) {
         else if (a == "--cus" && i + 1 < argc) o.pll_cus = std::atoi(argv[++i]);
         else if (a == "--tune" && i + 1 < argc) tune_path = argv[++i];
         else if (a == "--scan") scan = true;
+        else if (a == "--meter") meter = true;
         else if (a == "--scan-blocks" && i + 1 < argc) so.max_blocks = std::atoi(argv[++i]);
         else if (a == "--step" && i + 1 < argc) so.pick.step_khz = std::atoi(argv[++i]);
         else if (a == "--thr" && i + 1 < argc) so.pick.thr_db = (float)std::atof(argv[++i]);
@@ -68,7 +74,7 @@ int main(int argc, char** argv) {
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();
     if (scan) {
-        if (!tune_path.empty()) usage();   // a scan writes a tuning, it does not take one
+        if (!tune_path.empty() || meter) usage();   // a scan writes a tuning, it does not take one (nor does it demodulate)
         const std::string list = out + ".stations";
         so.nrows = o.nch;
         so.mode = o.mode;
@@ -110,7 +116,10 @@ int main(int argc, char** argv) {
         tune.khz = khz.data();
     }
     const int rows = tune_path.empty() ? o.nch : tune.nsrc;
-    const int rc = sdr_multi_run_tuned(&o, tune_path.empty() ? nullptr : &tune, &st);
+    sdr_meter_opts mo{};
+    sdr_meter_opts_default(&mo);
+    const sdr_multi_tuning* tp = tune_path.empty() ? nullptr : &tune;
+    const int rc = meter ? sdr_multi_run_metered(&o, tp, &mo, &st) : sdr_multi_run_tuned(&o, tp, &st);
     if (rc != SDR_OK) {
         std::fprintf(stderr, "sdr_multi: %d %s%s\n", rc, sdr_last_error(),
                      tune_path.empty() ? "" : " (--tune: 0 <= src < NCH rows, -N/2 < khz <= N/2, N = rf_Fs / 1000)");

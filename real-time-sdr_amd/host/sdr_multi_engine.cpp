@@ -14,6 +14,10 @@
 //           the write of block b-1 overlaps the GPU work of block b          stereo.cpp:69-114
 //   rds     wait_and_pop(1); sdr_push_fm_demod; rds_pre; PLL; rds_post; rds_bits -D2H-> host;
 //           frame sync per channel every 15 decoding blocks (host)          rds.cpp:95-192
+// A metered run (include/sdr_multi_meter.h) adds sdr_meter_audio after the audio thread's stereo_post
+// and sdr_meter_rds after the RDS thread's rds_post, each on its own context and post stream, both on
+// one shared meter; each thread copies the rows out behind its call and hands its part of block b to
+// MeterOut, which joins the two parts, writes PREFIX.meter and keeps the run's sums for PREFIX.status.
 // Streams (the four-queue budget of DESIGN.md 5): the producer's front end and both consumers' pre
 // parts share one stream (s_fe), both consumers' post parts another (s_post), and each consumer's
 // PLL has its own CU-masked stream -- with a known block count ONE persistent launch per consumer
@@ -47,6 +51,7 @@
 #include "rds_utilities.h"
 #include "sdr_amd.h"
 #include "sdr_multi.h"
+#include "sdr_multi_meter.h"
 #include "sdr_multi_tuned.h"
 
 using sdrhost::check_hip;
@@ -275,8 +280,81 @@ struct RdsRes {
     uint8_t *d_bits = nullptr, *h_bits[NH] = {};
 };
 
+// A metered run's host side. Each consumer copies the meter's rows out after its own call and takes
+// from the copy only the fields that call wrote (the other consumer may be writing its own meanwhile);
+// the block's row is complete, and written, when both parts are in. The consumers stay within a few
+// blocks of each other (the queue's prepare()), so few parts ever wait.
+struct MeterOut {
+    sdr_meter* m = nullptr;
+    sdr_meter_opts mo{};
+    int nch = 0, mode = 0;
+    uint8_t* h_rows[2][LAG + 1] = {};    // pinned, per consumer and rotation slot: nch rows
+    FILE* f = nullptr;                   // PREFIX.meter
+    std::mutex mu;
+    std::deque<std::pair<long long, std::vector<sdr_meter_row>>> pending[2];
+    long long blocks = 0;
+    struct Sum {
+        double v[5] = {};                // offset, level_db, pilot_nr, rds_nr, eye_db
+        long long flag[4] = {};          // blocks with STEREO, RDS, OFFTUNE, DEAD_AIR
+    };
+    std::vector<Sum> sum;
+    // consumer `which` (0 audio, 1 RDS) hands in its copy of block blk's rows
+    void part(long long blk, int which, const uint8_t* rows) {
+        std::vector<sdr_meter_row> mine((size_t)nch);
+        std::memcpy(mine.data(), rows, (size_t)nch * sizeof(sdr_meter_row));
+        std::lock_guard<std::mutex> lk(mu);
+        auto& other = pending[which ^ 1];
+        if (other.empty() || other.front().first != blk) {   // (both hand their blocks in ascending order)
+            pending[which].emplace_back(blk, std::move(mine));
+            return;
+        }
+        const std::vector<sdr_meter_row>& a = which == 0 ? mine : other.front().second;
+        const std::vector<sdr_meter_row>& r = which == 0 ? other.front().second : mine;
+        std::vector<sdr_meter_row> out(a);
+        for (int c = 0; c < nch; c++) {
+            sdr_meter_row& o = out[(size_t)c];
+            const sdr_meter_row& q = r[(size_t)c];
+            o.rds_sq = q.rds_sq;
+            o.eye_abs = q.eye_abs;
+            o.eye_sq = q.eye_sq;
+            o.eye_n = q.eye_n;
+            o.flags = (a[(size_t)c].flags & SDR_METER_ROW_AUDIO) | (q.flags & SDR_METER_ROW_RDS);
+            sdr_meter_state st{};
+            check_sdr(sdr_meter_status(mode, &o, &mo, &st), "sdr_meter_status");
+            Sum& s = sum[(size_t)c];
+            const double v[5] = {st.offset, st.level_db, st.pilot_nr, st.rds_nr, st.eye_db};
+            for (int i = 0; i < 5; i++) s.v[i] += v[i];
+            for (int i = 0; i < 4; i++) s.flag[i] += (st.flags >> i) & 1;
+        }
+        other.pop_front();
+        blocks++;
+        if (f && std::fwrite(out.data(), sizeof(sdr_meter_row), out.size(), f) != out.size()) die("cannot write the .meter file");
+    }
+    // PREFIX.status: per channel the run's means and the flags that held on more than half the blocks
+    void write_status(const std::string& path) const {
+        FILE* t = std::fopen(path.c_str(), "w");
+        if (!t) die("cannot write " + path);
+        static const char* names[4] = {"STEREO", "RDS", "OFFTUNE", "DEAD_AIR"};
+        for (int c = 0; c < nch; c++) {
+            const Sum& s = sum[(size_t)c];
+            const double n = blocks > 0 ? (double)blocks : 1.0;
+            std::fprintf(t, "ch %d: offset %.4f level_db %.2f pilot_nr %.3f rds_nr %.3f eye_db %.2f flags", c, s.v[0] / n,
+                         s.v[1] / n, s.v[2] / n, s.v[3] / n, s.v[4] / n);
+            bool any = false;
+            for (int i = 0; i < 4; i++)
+                if (2 * s.flag[i] > blocks) {
+                    std::fprintf(t, "%c%s", any ? '|' : ' ', names[i]);
+                    any = true;
+                }
+            std::fprintf(t, "%s\n", any ? "" : " -");
+        }
+        std::fclose(t);
+    }
+};
+
 struct Shared {
     sdr_multi_opts o{};
+    MeterOut* meter = nullptr;           // a metered run (sdr_multi_run_metered)
     int rows = 0;                        // input rows per block: nch, or a tuned run's nsrc
     bool tuned = false;
     AudioRes ar;
@@ -501,6 +579,7 @@ void audio_thread(Shared* sh) {
         const int h = (int)(blk % NH);
         wait_event(r.out_ready[h]);
         sh->d2h_ms += elapsed_ms(r.d0[h], r.d1[h]);
+        if (sh->meter) sh->meter->part(blk, 0, sh->meter->h_rows[0][h]);
         if (f) std::fwrite(r.h_lr[h], 1, bytes, f);
         if (o.cap_lr && blk < o.cap_blocks)
             for (int i = 0; i < o.ncap; i++)
@@ -515,6 +594,13 @@ void audio_thread(Shared* sh) {
         // d_lr[k] is free once block b-2's copy out of it is done (same stream, or the copy stream's event)
         if (sc != s && b >= 2) check_hip(hipStreamWaitEvent(s, r.out_ready[(b - 2) % NH], 0), "hipStreamWaitEvent");
         check_sdr(sdr_stereo_post(ctx, r.d_lr[k], n, s), "sdr_stereo_post");
+        if (MeterOut* mt = sh->meter) {
+            const sdr_meter_row* d_rows = nullptr;
+            check_sdr(sdr_meter_audio(mt->m, ctx, r.d_lr[k], n, s), "sdr_meter_audio");
+            check_sdr(sdr_meter_rows(mt->m, &d_rows), "sdr_meter_rows");
+            check_hip(hipMemcpyAsync(mt->h_rows[0][h], d_rows, (size_t)o.nch * sizeof(sdr_meter_row), hipMemcpyDeviceToHost, s),
+                      "hipMemcpyAsync");
+        }
         if (sc != s) {
             check_hip(hipEventRecord(r.post, s), "hipEventRecord");
             check_hip(hipStreamWaitEvent(sc, r.post, 0), "hipStreamWaitEvent");
@@ -556,6 +642,7 @@ void rds_thread(Shared* sh) {
     auto frame_layer = [&](long long blk) {   // rds.cpp:181-189 per channel; parse() prints to cerr
         const int k = (int)(blk % NH);
         wait_event(out_ready[k]);
+        if (sh->meter) sh->meter->part(blk, 1, sh->meter->h_rows[1][k]);
         if (o.cap_nbits && blk < o.cap_blocks)
             for (int i = 0; i < o.ncap; i++) {
                 o.cap_nbits[(size_t)blk * o.ncap + i] = h_nbits[k][o.cap_ch[i]];
@@ -591,6 +678,13 @@ void rds_thread(Shared* sh) {
         consumer_pll(sh, ctx, 1, pre, pll, b);
         const hipStream_t s = post_stream(sh, 1, b);
         check_sdr(sdr_rds_post(ctx, nullptr, 0, s), "sdr_rds_post");
+        if (MeterOut* mt = sh->meter) {
+            const sdr_meter_row* d_rows = nullptr;
+            check_sdr(sdr_meter_rds(mt->m, ctx, s), "sdr_meter_rds");
+            check_sdr(sdr_meter_rows(mt->m, &d_rows), "sdr_meter_rows");
+            check_hip(hipMemcpyAsync(mt->h_rows[1][k], d_rows, (size_t)o.nch * sizeof(sdr_meter_row), hipMemcpyDeviceToHost, s),
+                      "hipMemcpyAsync");
+        }
         check_sdr(sdr_rds_bits(ctx, nullptr, nullptr, nullptr, 0, d_nbits, d_bits, SDR_MAX_BITS, s), "sdr_rds_bits");
         check_hip(hipMemcpyAsync(h_nbits[k], d_nbits, o.nch * sizeof(int32_t), hipMemcpyDeviceToHost, s),
                   "hipMemcpyAsync");
@@ -734,7 +828,7 @@ bool tuning_valid(const sdr_multi_opts* o, const sdr_multi_tuning* t) {
     return true;
 }
 
-int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_multi_stats* stats) {
+int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo, sdr_multi_stats* stats) {
     if (!opts || opts->nch <= 0 || (!opts->in_path && (!opts->d_iq || opts->nblocks <= 0)))
         return SDR_E_INVALID;
     if (tune && !tuning_valid(opts, tune)) return SDR_E_INVALID;
@@ -810,6 +904,21 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_mult
     if (const char* e = std::getenv("SDR_MULTI_D2H"); e && std::strcmp(e, "copy") == 0) sh.s_d2h = plain_stream();
     mark("streams");
     alloc_consumers(&sh);
+    MeterOut meter;
+    if (mo) {
+        meter.mo = *mo;
+        meter.nch = o.nch;
+        meter.mode = o.mode;
+        meter.sum.resize((size_t)o.nch);
+        check_sdr(sdr_meter_create(&meter.m, o.device, o.nch, o.mode), "sdr_meter_create");
+        for (auto& per : meter.h_rows)
+            for (uint8_t*& p : per) pinned_get(&p, (size_t)o.nch * sizeof(sdr_meter_row));
+        if (o.out_prefix) {
+            meter.f = std::fopen((std::string(o.out_prefix) + ".meter").c_str(), "wb");
+            if (!meter.f) die(std::string("cannot write ") + o.out_prefix + ".meter");
+        }
+        sh.meter = &meter;
+    }
     mark("consumer buffers");
     // two recycled device batches of fm_demod [nch][block_if] (threadsafequeue.h's one slot, plus the
     // one the producer fills meanwhile)
@@ -877,6 +986,13 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_mult
         for (auto& e : fb.released) (void)hipEventDestroy(e);
     }
     free_consumers(&sh);
+    if (mo) {
+        if (meter.f) std::fclose(meter.f);
+        if (o.out_prefix) meter.write_status(std::string(o.out_prefix) + ".status");
+        for (auto& per : meter.h_rows)
+            for (uint8_t* p : per) pinned_put(p, (size_t)o.nch * sizeof(sdr_meter_row));
+        check_sdr(sdr_meter_destroy(meter.m), "sdr_meter_destroy");
+    }
     for (sdr_ctx* c : sh.ctx) ctx_put(c);
     if (sh.s_d2h) (void)hipStreamDestroy(sh.s_d2h);
     if (sh.s_post_c[1] != sh.s_post) release_masked(sh.s_post_c[1]);
@@ -896,8 +1012,16 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_mult
 
 }  // namespace
 
-extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats) { return multi_run(opts, nullptr, stats); }
+extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats) {
+    return multi_run(opts, nullptr, nullptr, stats);
+}
 
 extern "C" int sdr_multi_run_tuned(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_multi_stats* stats) {
-    return multi_run(opts, tune, stats);
+    return multi_run(opts, tune, nullptr, stats);
+}
+
+extern "C" int sdr_multi_run_metered(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo,
+                                     sdr_multi_stats* stats) {
+    if (!mo) return SDR_E_INVALID;
+    return multi_run(opts, tune, mo, stats);
 }
