@@ -307,6 +307,67 @@ int sdr_meter_rds(sdr_meter *m, sdr_ctx *ctx, void *stream);
 int sdr_meter_read(sdr_meter *m, sdr_meter_row *host_rows, void *stream);
 int sdr_meter_rows(sdr_meter *m, const sdr_meter_row **dev);   /* the device rows [nch] */
 
+/* ---- audio finishing (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
+ * de-emphasis, a stereo blend driven by the meter's pilot reading, and a gain, over the int16 rows
+ * sdr_stereo / sdr_stereo_post (width 2, L/R interleaved) or sdr_mono (width 1) wrote. The rows in and
+ * out are the caller's, so the stage is outside the parity-release protocol. N = n_audio,
+ * Fs_a = if_Fs * audio_upsample / audio_decim (48000, 40000, 44100, 44100 Hz in modes 0-3).
+ * Coefficients, on the host in double: a = RN32(exp(-1e6 / (tau_us Fs_a))), b = RN32(1 - (double)a);
+ * tau_us = 0: a = 0, b = 1, no de-emphasis.
+ * State per channel (sdr_audio_state): y[2], the current blend g0 and gain v0, the targets g1 and v1;
+ * after create and sdr_audio_reset y = 0 and g0 = g1 = v0 = v1 = 1.
+ * One call, frames n = 0 .. N-1, every f32 product and sum rounded on its own (no FMA), f32 subnormals
+ * kept: rN = fl(1.0f / (float)N), dg = fl(g1 - g0), dv = fl(v1 - v0), then
+ *   t = fl((float)(n + 1) rN),  g = fl(g0 + fl(dg t)),  v = fl(v0 + fl(dv t))
+ *   l = (float)L[n], r = (float)R[n],  m = 0.5f (l + r),  s = 0.5f (l - r)          (both exact)
+ *   p = fl(g s),  xl = fl(m + p),  xr = fl(m - p)
+ *   yl = fl(fl(a yl) + fl(b xl)), yr likewise
+ *   out = (int16) clamp(rintf(fl(v y)), -32767, 32767)     (rintf: to nearest even; -32768 is never
+ *                                                           made from audio, it stays SDR_PCM_POISON)
+ * and afterwards g0 := g1, v0 := v1: a change of blend or gain is a linear ramp over one block, free of
+ * clicks. Width 1: x = (float)s[n], one y, no blend. A row whose width N input samples all equal
+ * SDR_PCM_POISON is poisoned: its output is all SDR_PCM_POISON and the channel's y becomes 0; the ramps
+ * still advance. A channel's bytes do not depend on the batch it is in.
+ * Fidelity: the one-pole is the impulse-invariant filter, not the analogue RC network
+ * 1 / sqrt(1 + (2 pi f tau)^2): it attenuates LESS than the network by 0.01 dB at 1 kHz, 0.15-0.22 dB
+ * at 5 kHz, 0.6-0.9 dB at 10 kHz and 1.4-2.1 dB at 15 kHz (tau 50 and 75 us, the four audio rates). */
+typedef struct sdr_audio sdr_audio;
+typedef struct sdr_audio_opts {
+    float tau_us, blend_lo, blend_hi;
+} sdr_audio_opts;
+void sdr_audio_opts_default(sdr_audio_opts *o);   /* 75, 0.5, 2.0 */
+/* host only, no GPU: the one-pole's coefficients of a mode */
+int sdr_audio_coeffs(int mode, float tau_us, float *a, float *b);
+typedef struct sdr_audio_state {   /* 24 bytes */
+    float y[2], blend, gain, blend_target, gain_target;
+} sdr_audio_state;
+/* The stage is its own handle, like the meter. Every call enqueues on `stream` and returns;
+ * sdr_audio_read_state synchronises.
+ *   sdr_audio_set_control       blend and gain: host arrays [nch] of new targets, either may be NULL
+ *                               (that target stays); they take effect as a ramp over the next block
+ *   sdr_audio_blend_from_meter  the blend target of every channel from the meter's device row, in f32,
+ *                               n = block_if, q = n / 5 (integer): a row without SDR_METER_ROW_AUDIO leaves
+ *                               the target as it is; else P = fl(pilot_sq (float)q), Z = fl(noise_sq (float)n);
+ *                               !(P > 0): 0; Z == 0: 1; else min(max(fl(fl(fl(P / Z) - blend_lo) /
+ *                               fl(blend_hi - blend_lo)), 0), 1), NaN giving 0 (P / Z is the meter's
+ *                               pilot_nr; the division is the correctly rounded one). It must be ordered
+ *                               after the sdr_meter_audio whose row it reads: the same stream, or the caller.
+ *   sdr_audio_finish            one block: in [nch][>= width N] to out [nch][>= width N], strides in
+ *                               int16; out == in with equal strides is allowed, any other overlap is
+ *                               the caller's error
+ * SDR_E_INVALID, nothing enqueued: NULL handles or pointers, a bad mode, nch < 1, width not 1 or 2, tau_us
+ * negative, not finite or above 1000, blend_hi <= blend_lo, a blend outside [0, 1], a gain negative or not
+ * finite, a stride below width N or odd, a base not 4-byte aligned, a meter of another nch, mode or
+ * device. */
+int sdr_audio_create(sdr_audio **out, int device, int nch, int mode, int width, const sdr_audio_opts *o);
+int sdr_audio_destroy(sdr_audio *a);
+int sdr_audio_reset(sdr_audio *a, void *stream);
+int sdr_audio_set_control(sdr_audio *a, const float *blend, const float *gain, void *stream);
+int sdr_audio_blend_from_meter(sdr_audio *a, sdr_meter *m, void *stream);
+int sdr_audio_finish(sdr_audio *a, const int16_t *in, size_t in_stride, int16_t *out, size_t out_stride, void *stream);
+/* host [nch]; synchronises `stream` */
+int sdr_audio_read_state(sdr_audio *a, sdr_audio_state *host, void *stream);
+
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */

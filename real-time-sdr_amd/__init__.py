@@ -78,6 +78,16 @@ class MeterState(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("offset", "level_db", "pilot_nr", "rds_nr", "eye_db")] + [("flags", C.c_int)]
 
 
+class AudioOpts(C.Structure):
+    """sdr_audio_opts: the de-emphasis time constant and the blend map's two pilot_nr corners."""
+    _fields_ = [(n, C.c_float) for n in ("tau_us", "blend_lo", "blend_hi")]
+
+
+class AudioState(C.Structure):
+    """sdr_audio_state: one channel's filter state, current blend and gain and their targets, 24 bytes."""
+    _fields_ = [("y", C.c_float * 2)] + [(n, C.c_float) for n in ("blend", "gain", "blend_target", "gain_target")]
+
+
 METER_ROW_AUDIO, METER_ROW_RDS = 0x1, 0x2                                   # MeterRow.flags
 METER_STEREO, METER_RDS, METER_OFFTUNE, METER_DEAD_AIR = 0x1, 0x2, 0x4, 0x8   # MeterState.flags
 
@@ -163,6 +173,15 @@ def lib() -> C.CDLL:
         "sdr_meter_rds": ([vp, vp, vp], i32),
         "sdr_meter_read": ([vp, vp, vp], i32),
         "sdr_meter_rows": ([vp, C.POINTER(vp)], i32),
+        "sdr_audio_opts_default": ([C.POINTER(AudioOpts)], None),
+        "sdr_audio_coeffs": ([i32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)], i32),
+        "sdr_audio_create": ([C.POINTER(vp), i32, i32, i32, i32, C.POINTER(AudioOpts)], i32),
+        "sdr_audio_destroy": ([vp], i32),
+        "sdr_audio_reset": ([vp, vp], i32),
+        "sdr_audio_set_control": ([vp, vp, vp, vp], i32),
+        "sdr_audio_blend_from_meter": ([vp, vp, vp], i32),
+        "sdr_audio_finish": ([vp, vp, sz, vp, sz, vp], i32),
+        "sdr_audio_read_state": ([vp, vp, vp], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -464,6 +483,90 @@ class Meter:
     def status(self, stream=None, **opts):
         """meter_status of the current rows (synchronises the stream)."""
         return meter_status(self.mode, self.rows(stream), **opts)
+
+
+# ------------------------------------------------------------------ audio finishing (include/sdr_amd.h, sdr_audio_*)
+def audio_coeffs(mode: int, tau_us: float):
+    """(a, b) of the de-emphasis one-pole y = a y + b x at the mode's audio rate, as numpy float32
+    (host only): a = RN32(exp(-1e6 / (tau_us Fs_a))), b = RN32(1 - a); tau_us = 0 gives (0, 1)."""
+    import numpy as np
+    a, b = C.c_float(), C.c_float()
+    check(lib().sdr_audio_coeffs(mode, tau_us, C.byref(a), C.byref(b)), "sdr_audio_coeffs")
+    return np.float32(a.value), np.float32(b.value)
+
+
+def audio_opts(**opts) -> AudioOpts:
+    """The finishing stage's defaults (sdr_audio_opts_default) with the given fields replaced."""
+    o = AudioOpts()
+    lib().sdr_audio_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(AudioOpts._fields_):
+            raise SdrError(f"audio_opts: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+def audio_state_dtype():
+    """numpy dtype of sdr_audio_state (24 bytes)."""
+    import numpy as np
+    return np.dtype(AudioState)
+
+
+class AudioFinish:
+    """The finishing stage of `nch` channels of one mode (sdr_audio_*): de-emphasis, stereo blend and
+    gain over the int16 rows stereo() (width 2) or mono() (width 1) wrote. Per block, optionally
+    set_control(blend, gain) or blend_from_meter(meter) after meter.audio, then finish(lr). Its own handle;
+    the state stays on the device. opts: tau_us (75; 50 outside the Americas; 0 off), blend_lo, blend_hi."""
+
+    def __init__(self, nch: int, mode: int = 0, width: int = 2, device: int = 0, **opts):
+        h = C.c_void_p()
+        o = audio_opts(**opts)
+        check(lib().sdr_audio_create(C.byref(h), device, nch, mode, width, C.byref(o)), "sdr_audio_create")
+        self._h = h
+        self.nch, self.mode, self.width, self.device = nch, mode, width, device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sdr_audio_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().sdr_audio_reset(self._h, _stream(stream)), "sdr_audio_reset")
+
+    def set_control(self, blend=None, gain=None, stream=None):
+        """New targets per channel (a scalar serves every channel): blend in [0, 1] (0 mono, 1 full
+        stereo), gain >= 0 (0 mutes); each is reached by a linear ramp over the next block."""
+        import numpy as np
+        arr = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (self.nch,)))
+               for v in (blend, gain)]
+        ptr = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arr]
+        check(lib().sdr_audio_set_control(self._h, ptr[0], ptr[1], _stream(stream)), "sdr_audio_set_control")
+
+    def blend_from_meter(self, meter: "Meter", stream=None):
+        """The blend targets from the meter's current rows (after meter.audio of the block, same stream)."""
+        check(lib().sdr_audio_blend_from_meter(self._h, meter._h, _stream(stream)), "sdr_audio_blend_from_meter")
+
+    def finish(self, lr, out=None, stream=None):
+        """One block: lr int16 [nch][>= width * n_audio] to out (a new tensor when None; out may be lr)."""
+        import torch
+        if out is None:
+            out = torch.empty(self.nch, lr.shape[1], dtype=torch.int16, device=lr.device)
+        check(lib().sdr_audio_finish(self._h, _ptr(lr), _row_stride(lr), _ptr(out), _row_stride(out), _stream(stream)),
+              "sdr_audio_finish")
+        return out
+
+    def state(self, stream=None):
+        """numpy structured array [nch] of audio_state_dtype(); synchronises the stream."""
+        import numpy as np
+        out = np.zeros(self.nch, audio_state_dtype())
+        check(lib().sdr_audio_read_state(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_audio_read_state")
+        return out
 
 
 # ------------------------------------------------------------------ batched primitives (torch tensors)

@@ -2,6 +2,7 @@
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
 //   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
+//             [--deemph US] [--blend]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //
 // Input: u8 I/Q, block after block, each block NCH rows of 2*block_iq bytes (channel after
@@ -19,7 +20,10 @@
 // n the scan printed then receives them. --meter: the reception meter (include/sdr_multi_meter.h) beside the
 // receiver, with or without --tune -- PREFIX.meter (per block NCH rows of 64 bytes, sdr_meter_row) and
 // PREFIX.status (per channel the run's mean readings and its STEREO / RDS / OFFTUNE / DEAD_AIR flags);
-// the PCM and the RDS text are those of a run without it.
+// the PCM and the RDS text are those of a run without it. --deemph US (0, 50 or 75) and --blend (needs
+// --meter): the audio finishing stage (include/sdr_multi_audio.h) -- PREFIX.audio, in the layout of PREFIX.pcm,
+// holds the audio de-emphasised with US microseconds (75 when only --blend is given) and, with --blend,
+// blended to mono where the meter finds no pilot; every other file is that of a run without them.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +32,7 @@
 
 #include "sdr_amd.h"
 #include "sdr_multi.h"
+#include "sdr_multi_audio.h"
 #include "sdr_multi_meter.h"
 #include "sdr_multi_tuned.h"
 #include "sdr_scan_run.h"
@@ -35,11 +40,13 @@
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
-                         "[--tune FILE] [--meter]\n"
+                         "[--tune FILE] [--meter] [--deemph US] [--blend]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
                          "  --tune FILE: NCH lines \"src khz\"; the input holds max(src)+1 capture rows per block\n"
                          "  --meter: also write PREFIX.meter (64-byte readings per channel and block) and PREFIX.status\n"
+                         "  --deemph US: also write PREFIX.audio, the PCM de-emphasised with 0, 50 or 75 microseconds\n"
+                         "  --blend: PREFIX.audio blended to mono where the meter finds no pilot (needs --meter)\n"
                          "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n");
     std::exit(1);
 }
@@ -52,7 +59,9 @@ int main(int argc, char** argv) {
     o.pll_cus = 64;
     std::string in = "-", out = "sdr_multi", tune_path;
     if (o.nch <= 0) usage();
-    bool scan = false, meter = false;
+    bool scan = false, meter = false, blend = false, finish = false;
+    sdr_audio_opts ao{};
+    sdr_audio_opts_default(&ao);
     sdr_scan_run_opts so{};
     sdr_scan_opts_default(&so.pick);
     for (int i = 2; i < argc; i++) {
@@ -64,6 +73,13 @@ int main(int argc, char** argv) {
         else if (a == "--tune" && i + 1 < argc) tune_path = argv[++i];
         else if (a == "--scan") scan = true;
         else if (a == "--meter") meter = true;
+        else if (a == "--blend") blend = finish = true;
+        else if (a == "--deemph" && i + 1 < argc) {
+            const std::string us = argv[++i];
+            if (us != "0" && us != "50" && us != "75") usage();
+            ao.tau_us = (float)std::atoi(us.c_str());
+            finish = true;
+        }
         else if (a == "--scan-blocks" && i + 1 < argc) so.max_blocks = std::atoi(argv[++i]);
         else if (a == "--step" && i + 1 < argc) so.pick.step_khz = std::atoi(argv[++i]);
         else if (a == "--thr" && i + 1 < argc) so.pick.thr_db = (float)std::atof(argv[++i]);
@@ -73,8 +89,9 @@ int main(int argc, char** argv) {
     if (const char* dev = std::getenv("SDR_DEVICE")) o.device = std::atoi(dev);
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();
+    if (blend && !meter) usage();
     if (scan) {
-        if (!tune_path.empty() || meter) usage();   // a scan writes a tuning, it does not take one (nor does it demodulate)
+        if (!tune_path.empty() || meter || finish) usage();   // a scan writes a tuning, it does not take one (nor does it demodulate)
         const std::string list = out + ".stations";
         so.nrows = o.nch;
         so.mode = o.mode;
@@ -119,7 +136,9 @@ int main(int argc, char** argv) {
     sdr_meter_opts mo{};
     sdr_meter_opts_default(&mo);
     const sdr_multi_tuning* tp = tune_path.empty() ? nullptr : &tune;
-    const int rc = meter ? sdr_multi_run_metered(&o, tp, &mo, &st) : sdr_multi_run_tuned(&o, tp, &st);
+    const int rc = finish  ? sdr_multi_run_finished(&o, tp, meter ? &mo : nullptr, &ao, blend ? 1 : 0, &st)
+                   : meter ? sdr_multi_run_metered(&o, tp, &mo, &st)
+                           : sdr_multi_run_tuned(&o, tp, &st);
     if (rc != SDR_OK) {
         std::fprintf(stderr, "sdr_multi: %d %s%s\n", rc, sdr_last_error(),
                      tune_path.empty() ? "" : " (--tune: 0 <= src < NCH rows, -N/2 < khz <= N/2, N = rf_Fs / 1000)");

@@ -18,6 +18,9 @@
 // and sdr_meter_rds after the RDS thread's rds_post, each on its own context and post stream, both on
 // one shared meter; each thread copies the rows out behind its call and hands its part of block b to
 // MeterOut, which joins the two parts, writes PREFIX.meter and keeps the run's sums for PREFIX.status.
+// A finished run (include/sdr_multi_audio.h) adds, behind them on the audio thread's post stream,
+// sdr_audio_blend_from_meter (with --blend) and sdr_audio_finish from the block's L/R rows into rows of
+// its own, copied out behind the L/R copy and written to PREFIX.audio.
 // Streams (the four-queue budget of DESIGN.md 5): the producer's front end and both consumers' pre
 // parts share one stream (s_fe), both consumers' post parts another (s_post), and each consumer's
 // PLL has its own CU-masked stream -- with a known block count ONE persistent launch per consumer
@@ -51,6 +54,7 @@
 #include "rds_utilities.h"
 #include "sdr_amd.h"
 #include "sdr_multi.h"
+#include "sdr_multi_audio.h"
 #include "sdr_multi_meter.h"
 #include "sdr_multi_tuned.h"
 
@@ -352,9 +356,18 @@ struct MeterOut {
     }
 };
 
+// A finished run's audio side: the stage, its device rows (two, as d_lr) and pinned copies (as h_lr)
+struct AudioFin {
+    sdr_audio* a = nullptr;
+    bool blend = false;                  // the blend targets follow the meter's rows
+    int16_t *d_out[2] = {}, *h_out[LAG + 1] = {};
+    FILE* f = nullptr;                   // PREFIX.audio
+};
+
 struct Shared {
     sdr_multi_opts o{};
     MeterOut* meter = nullptr;           // a metered run (sdr_multi_run_metered)
+    AudioFin* fin = nullptr;             // a finished run (sdr_multi_run_finished)
     int rows = 0;                        // input rows per block: nch, or a tuned run's nsrc
     bool tuned = false;
     AudioRes ar;
@@ -581,6 +594,8 @@ void audio_thread(Shared* sh) {
         sh->d2h_ms += elapsed_ms(r.d0[h], r.d1[h]);
         if (sh->meter) sh->meter->part(blk, 0, sh->meter->h_rows[0][h]);
         if (f) std::fwrite(r.h_lr[h], 1, bytes, f);
+        if (sh->fin && sh->fin->f && std::fwrite(sh->fin->h_out[h], 1, bytes, sh->fin->f) != bytes)
+            die("cannot write the .audio file");
         if (o.cap_lr && blk < o.cap_blocks)
             for (int i = 0; i < o.ncap; i++)
                 std::memcpy(o.cap_lr + ((size_t)blk * o.ncap + i) * n, r.h_lr[h] + (size_t)o.cap_ch[i] * n,
@@ -601,6 +616,11 @@ void audio_thread(Shared* sh) {
             check_hip(hipMemcpyAsync(mt->h_rows[0][h], d_rows, (size_t)o.nch * sizeof(sdr_meter_row), hipMemcpyDeviceToHost, s),
                       "hipMemcpyAsync");
         }
+        AudioFin* af = sh->fin;
+        if (af) {   // d_out[k] is free as d_lr[k] is: its copy of block b-2 precedes out_ready
+            if (af->blend) check_sdr(sdr_audio_blend_from_meter(af->a, sh->meter->m, s), "sdr_audio_blend_from_meter");
+            check_sdr(sdr_audio_finish(af->a, r.d_lr[k], n, af->d_out[k], n, s), "sdr_audio_finish");
+        }
         if (sc != s) {
             check_hip(hipEventRecord(r.post, s), "hipEventRecord");
             check_hip(hipStreamWaitEvent(sc, r.post, 0), "hipStreamWaitEvent");
@@ -608,6 +628,7 @@ void audio_thread(Shared* sh) {
         check_hip(hipEventRecord(r.d0[h], sc), "hipEventRecord");
         check_hip(hipMemcpyAsync(r.h_lr[h], r.d_lr[k], bytes, hipMemcpyDeviceToHost, sc), "hipMemcpyAsync");
         check_hip(hipEventRecord(r.d1[h], sc), "hipEventRecord");
+        if (af) check_hip(hipMemcpyAsync(af->h_out[h], af->d_out[k], bytes, hipMemcpyDeviceToHost, sc), "hipMemcpyAsync");
         check_hip(hipEventRecord(r.out_ready[h], sc), "hipEventRecord");
         if (b >= LAG) write_block(b - LAG);                 // overlaps the GPU work of blocks b-1, b
         b++;
@@ -828,7 +849,8 @@ bool tuning_valid(const sdr_multi_opts* o, const sdr_multi_tuning* t) {
     return true;
 }
 
-int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo, sdr_multi_stats* stats) {
+int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo, const sdr_audio_opts* ao,
+              bool blend, sdr_multi_stats* stats) {
     if (!opts || opts->nch <= 0 || (!opts->in_path && (!opts->d_iq || opts->nblocks <= 0)))
         return SDR_E_INVALID;
     if (tune && !tuning_valid(opts, tune)) return SDR_E_INVALID;
@@ -919,6 +941,20 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
         }
         sh.meter = &meter;
     }
+    AudioFin fin;
+    const size_t fin_bytes = 2 * (size_t)sh.info.n_audio * o.nch * sizeof(int16_t);
+    if (ao) {
+        fin.blend = blend;
+        check_sdr(sdr_audio_create(&fin.a, o.device, o.nch, o.mode, 2, ao), "sdr_audio_create");
+        check_sdr(sdr_audio_reset(fin.a, nullptr), "sdr_audio_reset");   // (synchronised with the batches below)
+        for (auto& p : fin.d_out) check_hip(hipMalloc(reinterpret_cast<void**>(&p), fin_bytes), "hipMalloc");
+        for (auto& p : fin.h_out) pinned_get(&p, fin_bytes);
+        if (o.out_prefix) {
+            fin.f = std::fopen((std::string(o.out_prefix) + ".audio").c_str(), "wb");
+            if (!fin.f) die(std::string("cannot write ") + o.out_prefix + ".audio");
+        }
+        sh.fin = &fin;
+    }
     mark("consumer buffers");
     // two recycled device batches of fm_demod [nch][block_if] (threadsafequeue.h's one slot, plus the
     // one the producer fills meanwhile)
@@ -993,6 +1029,12 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
             for (uint8_t* p : per) pinned_put(p, (size_t)o.nch * sizeof(sdr_meter_row));
         check_sdr(sdr_meter_destroy(meter.m), "sdr_meter_destroy");
     }
+    if (ao) {
+        if (fin.f) std::fclose(fin.f);
+        for (auto& p : fin.h_out) pinned_put(p, fin_bytes);
+        for (auto& p : fin.d_out) (void)hipFree(p);
+        check_sdr(sdr_audio_destroy(fin.a), "sdr_audio_destroy");
+    }
     for (sdr_ctx* c : sh.ctx) ctx_put(c);
     if (sh.s_d2h) (void)hipStreamDestroy(sh.s_d2h);
     if (sh.s_post_c[1] != sh.s_post) release_masked(sh.s_post_c[1]);
@@ -1013,15 +1055,23 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
 }  // namespace
 
 extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats) {
-    return multi_run(opts, nullptr, nullptr, stats);
+    return multi_run(opts, nullptr, nullptr, nullptr, false, stats);
 }
 
 extern "C" int sdr_multi_run_tuned(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_multi_stats* stats) {
-    return multi_run(opts, tune, nullptr, stats);
+    return multi_run(opts, tune, nullptr, nullptr, false, stats);
 }
 
 extern "C" int sdr_multi_run_metered(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo,
                                      sdr_multi_stats* stats) {
     if (!mo) return SDR_E_INVALID;
-    return multi_run(opts, tune, mo, stats);
+    return multi_run(opts, tune, mo, nullptr, false, stats);
+}
+
+extern "C" int sdr_multi_run_finished(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo,
+                                      const sdr_audio_opts* ao, int blend, sdr_multi_stats* stats) {
+    if (!opts || !ao || (blend && !mo)) return SDR_E_INVALID;
+    float a = 0.0f, b = 0.0f;   // what sdr_audio_create would refuse, before anything starts
+    if (sdr_audio_coeffs(opts->mode, ao->tau_us, &a, &b) != SDR_OK || !(ao->blend_hi > ao->blend_lo)) return SDR_E_INVALID;
+    return multi_run(opts, tune, mo, ao, blend != 0, stats);
 }
