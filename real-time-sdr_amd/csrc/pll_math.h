@@ -328,8 +328,8 @@ PLLM_HD SinCosR sincos_r(float t) {
 //  * sincos_rn: the reduction rounds -t (2/pi) against MAGIC + 1, so the low word of the rounded
 //    value is nq1 = 1 - q (mod 2^32) -- exactly what base_angle needs -- and kdn = -kd folds its
 //    sign into the two reduction fmas. Both kernels by Horner (2 multiplies fewer than Estrin's
-//    z^2, z^4 powers, a longer dependent chain: +1.8 %; a two-level form, +3.4 %, is
-//    tools/patches/pll_variants.patch) with the refitted 5-coefficient sin (SR1..SR5, one fma fewer
+//    z^2, z^4 powers, a longer dependent chain: +1.8 %; a two-level form, +3.4 %, is recorded
+//    in profiles/HISTORY.md) with the refitted 5-coefficient sin (SR1..SR5, one fma fewer
 //    than fdlibm's).
 //  * base_angle_n(nlo, nq1, b, mr) = base_angle(nlo, 1 - nq1, b, mr): one 3-input add.
 // ------------------------------------------------------------------------------------------

@@ -74,8 +74,8 @@ struct PllJob {
     // pll_math.h pll_rx of every input sample (written by the producer of `in`)
     const double* rx;
     size_t rx_stride;
-    // -in (written by the producer; row stride neg_stride): with it the PLL runs on lane pairs
-    // (sdr_pll.hip pll_run_split)
+    // -in (written by the producer; row stride neg_stride). Required, like rx: the PLL runs on lane
+    // pairs, and the even lane of a pair takes -in (sdr_pll.hip pll_step_split)
     const float* in_neg;
     size_t neg_stride;
 };

@@ -1,6 +1,6 @@
 // sdr_pll.hip -- the PLL / NCO recurrence of the FM/RDS hot path on MI355X (gfx950):
-//   fmpll, pll.cpp:4-61 (pllblock_args, include/pll.h:10-20), one lane per channel, with
-//   pll_math.h's correctly-rounded fast paths and double-double fallbacks (DESIGN.md 4a);
+//   fmpll, pll.cpp:4-61 (pllblock_args, include/pll.h:10-20), a lane pair per channel, with
+//   pll_math.h's correctly-rounded fast paths and double-double fallbacks (DESIGN.md 4a, 4c);
 //   the persistent multi-block launch and its stream hand-offs.
 #include "sdr_internal.h"
 
@@ -8,7 +8,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 
 #include "pll_math.h"
 
@@ -17,19 +16,22 @@
 namespace sdrk {
 namespace {
 // ------------------------------------------------------------------------------------------
-// PLL / NCO, pll.cpp:4-61. One lane per channel: the recurrence is serial in time.
+// PLL / NCO, pll.cpp:4-61. The recurrence is serial in time; a lane pair runs each channel.
 //
-// k_pll_libm: the literal restatement (f64 OCML atan2/sincos per step), kept as the A/B
-// reference (flag SDR_FLAG_PLL_LIBM) and used for chunk redo.
-// k_pll: the same recurrence with pll_math.h's correctly-rounded fast paths. Each 64-step chunk
-// runs branch-free; if any step of a lane reported an ambiguous f32 rounding (~6.6e-6 per step)
-// the lane restores its chunk snapshot and redoes the chunk with per-step f64-libm fallbacks.
-// Both write out[0] = lastCarrier and out[i+1] = t_i (the f32 NCO phase); k_nco_out then turns
+// k_pll_libm: the literal restatement (f64 OCML atan2/sincos per step, one lane per channel), kept
+// as the A/B reference (flag SDR_FLAG_PLL_LIBM).
+// k_pll, k_pll_multi: the same recurrence with pll_math.h's correctly-rounded fast paths, on lane
+// pairs (pll_step_split below: lanes 2k and 2k+1 share the step of channel k). Each 16-step chunk
+// (PLL_CHUNK) runs branch-free from one of PLL_NBUF register buffers of prefetched inputs; if a
+// step of either lane could not prove its f32 roundings, the pair restores its chunk snapshot and
+// redoes the chunk with the full-lane checked step (pll_step_checked), whose fallbacks return the
+// reference's f64-libm values.
+// All write out[0] = lastCarrier and out[i+1] = t_i (the f32 NCO phase); k_nco_out then turns
 // t_i into cos(t_i*ncoScale + phaseAdjust) in parallel (pll.cpp:52) and updates lastCarrier.
 // ------------------------------------------------------------------------------------------
 struct PllRegs {
     float fbI, fbQ;              // in the reduced frame: RN(cos r), RN(sin r) (pll_math.h)
-    f32x2 ip;                    // {integrator, phaseEst}: one packed multiply and add per step
+    f32x2 ip;                    // {integrator, phaseEst} (the state's words; stepped as scalar f32)
     double toff;
     double c, s, mr;             // f64 cos r, sin r and -r of the previous step's t = q pi/2 + r
     uint32_t nq1, b;             // 1 - q (mod 2^32) for its quadrant q, and [r < 0]
@@ -81,15 +83,14 @@ __device__ __forceinline__ PllRegs pll_load(const sdr_pll_state& st, double w) {
 //     table (TAB) the launch checked |w| (|toff| + n + 1) < 1.375 * 2^29, which leaves room for
 //     |phaseEst| < 2^28 plus 16 steps of drift; without it the chunk's largest |t| is tracked.
 struct PllProof {
-    double emax = 0.0;
-    float emaxf = 0.0f;     // lane-pair steps: max |RN32(ed)| (PLL_EMAX_F)
+    float emaxf = 0.0f;     // max |RN32(ed)| (PLL_EMAX_F)
     uint32_t split = 0u;
     uint32_t tie = ~0u;
     float tmax = 0.0f;
 };
 // (the A/B variants of this step measured and dropped -- e bracket order, bracket by fma, pre-loop
 // wait, packed loop filter, first table entries carried, one lane per chain, no trigArg table -- are
-// kept as tools/patches/pll_variants.patch)
+// recorded in profiles/HISTORY.md)
 // |e| bound of the fast phase detector (the wrap to [-pi, pi] is the reference's below it)
 constexpr double PLL_EMAX = pllm::PI - 0x1p-30;
 // the largest f32 below PLL_EMAX: RN32 is monotone, so |RN32(ed)| < PLL_EMAX_F implies |ed| < PLL_EMAX_F
@@ -156,14 +157,6 @@ constexpr int PLL_HWID_SLOTS = 4096, PLL_HWID_FIELDS = 5;
 __device__ unsigned long long g_pll_hwid[PLL_HWID_SLOTS][PLL_HWID_FIELDS];
 #endif
 
-// TAB: the trigArg offsets come from a table whose range the kernel checked once (pll_run)
-template <bool TAB>
-__device__ __forceinline__ bool pll_chunk_ok(const PllProof& pf, const PllRegs& r, double w, int chunk) {
-    return (pf.emax < PLL_EMAX) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
-           (__builtin_fabs(r.ip.y) < 0x1p28f) & (__builtin_fabs(r.ip.x) < 0x1p20f) &
-           (TAB || (pf.tmax < 0x1p30f));
-}
-
 // the f64 libm results of the reference step (pll.cpp:39, :49-50), out of line: only the rare
 // fallbacks call them, and the unrolled redo chunks stay small. They return glibc's value RN64(f)
 // from double-double evaluations (pll_math.h), not the device libm's, which differs from glibc by
@@ -189,19 +182,12 @@ __device__ __forceinline__ uint32_t or_xor(uint32_t acc, uint32_t lo, uint32_t h
     return d;
 }
 
-// tie accumulator: min(acc, tc, ts) as one v_min3_u32 (the compiler otherwise pairs the keys of
-// consecutive steps into a v_min_u32 + v_min3_u32 tree)
-__device__ __forceinline__ uint32_t min3_u32(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t d;
-    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-
-// One step of pll.cpp:36-50. CHECKED: every result the fast path cannot prove is recomputed
-// with the f64 libm exactly as the reference (used for chunk redo and short tails).
-template <bool CHECKED, bool TAB>
-__device__ __forceinline__ void pll_step(PllRegs& r, float x, double rx, float Kp, float Ki, double w, double wt,
-                                         float& t_out, PllProof& pf) {
+// One step of pll.cpp:36-50 on a full lane (every lane of a pair runs it with the same values):
+// every result the fast path cannot prove is recomputed with the f64 libm exactly as the reference.
+// Used for chunk redo and short tails.
+template <bool TAB>
+__device__ __forceinline__ void pll_step_checked(PllRegs& r, float x, double rx, float Kp, float Ki, double w,
+                                                 double wt, float& t_out) {
     // pll.cpp:36-37 in the reduced frame, as one packed multiply: x * (fbI, -fbQ)
     typedef float f2v __attribute__((ext_vector_type(2)));
     const f2v fb = {r.fbI, -r.fbQ};
@@ -216,19 +202,13 @@ __device__ __forceinline__ void pll_step(PllRegs& r, float x, double rx, float K
     const float hi = (float)(ed + pllm::EPS_ABS_E2);
     const float lo = (float)(ed - pllm::EPS_ABS_E2);
     float e = hi;                                             // = RN32(ed) whenever lo == hi
-    if (CHECKED) {
-        if (!((__builtin_fabs(ed) < PLL_EMAX) && lo == hi)) {
-            float a = eI0, b = -eQ0;                          // eI - i eQ = i^q (eI0 - i eQ0)
-            pllm::rot_q(1u - r.nq1, a, b);
-            e = pll_atan2_ref(-b, a);                         // pll.cpp:39
-        }
-    } else {
-        pf.emax = fmax(pf.emax, __builtin_fabs(ed));
-        pf.split = or_xor(pf.split, __builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi));
+    if (!((__builtin_fabs(ed) < PLL_EMAX) && lo == hi)) {
+        float a = eI0, b = -eQ0;                              // eI - i eQ = i^q (eI0 - i eQ0)
+        pllm::rot_q(1u - r.nq1, a, b);
+        e = pll_atan2_ref(-b, a);                             // pll.cpp:39
     }
-    // pll.cpp:41-42: integ += Ki e; phaseEst = (phaseEst + Kp e) + integ, as scalar f32 (5 VALU,
-    // no hazard wait states after packed-f32 results: +1.2 % against the packed form,
-    // profiles/r02/ab_pll_lf.txt)
+    // pll.cpp:41-42: integ += Ki e; phaseEst = (phaseEst + Kp e) + integ, as scalar f32 (the
+    // reference's five operations; the fast step keeps one state word per lane, pll_step_split)
     {
         const float ki_e = Ki * e;
         const float integ = r.ip.x + ki_e;
@@ -250,21 +230,16 @@ __device__ __forceinline__ void pll_step(PllRegs& r, float x, double rx, float K
     r.b = sc.b;
     r.fbI = (float)sc.cr;                                     // pll.cpp:49-50, reduced frame
     r.fbQ = (float)sc.sr;
-    if (CHECKED) {
-        const bool in_range = __builtin_fabs((double)t) < pllm::T_MAX;
-        if (!(in_range && sc.tie > pllm::TIE_MIN)) {
-            double sv, cv;
-            pll_sincos_ref(t, &sv, &cv);
-            pllm::rot_q(r.nq1 - 1u, cv, sv);                  // into the reduced frame, exactly
-            r.fbI = (float)cv;
-            r.fbQ = (float)sv;
-            r.c = cv;
-            r.s = sv;
-            if (!in_range) r.mr = __builtin_nan("");
-        }
-    } else {
-        pf.tie = min3_u32(pf.tie, sc.tc, sc.ts);
-        if (!TAB) pf.tmax = fmaxf(pf.tmax, __builtin_fabsf(t));
+    const bool in_range = __builtin_fabs((double)t) < pllm::T_MAX;
+    if (!(in_range && sc.tie > pllm::TIE_MIN)) {
+        double sv, cv;
+        pll_sincos_ref(t, &sv, &cv);
+        pllm::rot_q(r.nq1 - 1u, cv, sv);                      // into the reduced frame, exactly
+        r.fbI = (float)cv;
+        r.fbQ = (float)sv;
+        r.c = cv;
+        r.s = sv;
+        if (!in_range) r.mr = __builtin_nan("");
     }
     t_out = t;
 }
@@ -278,146 +253,8 @@ constexpr int PLL_CHUNK = SDR_PLL_CHUNK;
 #endif
 constexpr int PLL_NBUF = SDR_PLL_NBUF;   // register buffers of inputs (prefetch distance NBUF - 1 chunks)
 
-// VEC: x / rx rows and the t buffer are 16-byte aligned with strides that are multiples of 4
-// (x, t) and 2 (rx), so a chunk's inputs are prefetched with 16-byte loads one chunk ahead and
-// the 16 phases are stored with 16-byte stores -- the unrolled chunk itself touches no memory.
-// One lane per channel runs the n serial steps of one PllJob.
-// TAB: every lane of the wave has the same trigOffset (a context's channels advance together), so
-// w * trigOffset of every step comes from a table the wave builds in LDS up front (pll.cpp:46-47
-// evaluated once per step index instead of once per channel and step).
-template <bool VEC, bool TAB>
-__device__ __forceinline__ void pll_run(const PllJob& jb, int n, int ch, const double* __restrict__ wtab) {
-    const float* __restrict__ in = jb.in;
-    const size_t in_stride = jb.in_stride, t_stride = jb.t_stride, out_stride = jb.out_stride;
-    float* __restrict__ tbuf = jb.tbuf;
-    float* __restrict__ out = jb.out;
-    sdr_pll_state* __restrict__ st = jb.st;
-    const float freq = jb.freq, Fs = jb.Fs, normBandwidth = jb.bw;
-    const float Cp = 2.666;
-    const float Ci = 3.555;
-    const float Kp = normBandwidth * Cp;
-    const float Ki = normBandwidth * normBandwidth * Ci;
-    const double w = 2 * 3.14159265358979323846 * (freq / Fs);
-    const sdr_pll_state s0 = st[ch];
-    const float* x = in + (size_t)ch * in_stride;
-    const double* rxp = jb.rx + (size_t)ch * jb.rx_stride;
-    float* tb = tbuf + (size_t)ch * t_stride;
-    if (!jb.prev_out) out[(size_t)ch * out_stride] = s0.lastCarrier;   // pll.cpp:18
-    PllRegs r = pll_load(s0, w);
-    // Chunks rotate through PLL_NBUF register buffers: chunk c computes from buffer c % NBUF, stores
-    // its phases, then refills that buffer with chunk c + NBUF. A chunk's inputs are thus loaded
-    // NBUF - 1 chunks ahead and, being issued after the previous chunk's stores, never make a
-    // wait include those stores (vmcnt counts loads and stores in issue order). The main loop
-    // covers a multiple of NBUF chunks; the rest (< NBUF chunks + n % CHUNK) runs checked steps.
-    constexpr int C = PLL_CHUNK, NB = PLL_NBUF;
-    const int nchunks = n / C;
-    const int nmain = nchunks - nchunks % NB;
-    float xb[NB][C];
-    double rb[NB][C];
-    auto load_chunk = [&](float* dx, double* dr, int i0) {
-        if (VEC) {
-#pragma unroll
-            for (int k = 0; k < C / 4; k++) {
-                const float4 v = reinterpret_cast<const float4*>(x + i0)[k];
-                dx[4 * k] = v.x; dx[4 * k + 1] = v.y; dx[4 * k + 2] = v.z; dx[4 * k + 3] = v.w;
-            }
-#pragma unroll
-            for (int k = 0; k < C / 2; k++) {
-                const double2 v = reinterpret_cast<const double2*>(rxp + i0)[k];
-                dr[2 * k] = v.x; dr[2 * k + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < C; k++) {
-                dx[k] = x[i0 + k];
-                dr[k] = rxp[i0 + k];
-            }
-        }
-    };
-    if (nmain > 0) {
-#pragma unroll
-        for (int u = 0; u < NB; u++) load_chunk(xb[u], rb[u], u * C);
-    }
-    for (int c0 = 0; c0 < nmain; c0 += NB) {
-#pragma unroll
-        for (int u = 0; u < NB; u++) {
-            const int i0 = (c0 + u) * C;
-            double wv[C];
-            if (TAB) {
-#pragma unroll
-                for (int k = 0; k < C / 2; k++) {
-                    const double2 v = reinterpret_cast<const double2*>(wtab + i0)[k];
-                    wv[2 * k] = v.x; wv[2 * k + 1] = v.y;
-                }
-            }
-            const PllRegs snap = r;
-            PllProof pf;
-            float tv[C];
-#pragma unroll
-            for (int j = 0; j < C; j++)
-                pll_step<false, TAB>(r, xb[u][j], rb[u][j], Kp, Ki, w, TAB ? wv[j] : 0.0, tv[j], pf);
-            const bool chunk_ok = pll_chunk_ok<TAB>(pf, r, w, C);
-#if SDR_PLL_COUNT
-            pll_count_chunk(chunk_ok);
-#endif
-            if (!chunk_ok) {
-                r = snap;
-#pragma unroll
-                for (int j = 0; j < C; j++)
-                    pll_step<true, TAB>(r, xb[u][j], rb[u][j], Kp, Ki, w, TAB ? wv[j] : 0.0, tv[j], pf);
-            }
-            if (VEC) {
-#pragma unroll
-                for (int k = 0; k < C / 4; k++)
-                    reinterpret_cast<float4*>(tb + i0)[k] = make_float4(tv[4 * k], tv[4 * k + 1], tv[4 * k + 2], tv[4 * k + 3]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < C; k++) tb[i0 + k] = tv[k];
-            }
-            // refill (the last refills re-read the final chunk: harmless, keeps the loop branch-free)
-            load_chunk(xb[u], rb[u], min(c0 + u + NB, nmain - 1) * C);
-        }
-    }
-    {
-        // the rest (< NB chunks + n % C steps), checked, from register buffers loaded one piece
-        // ahead (one exposed memory latency for the whole rest instead of one per step)
-        PllProof pf;
-        const int i_rest = nmain * C;
-        float xr[C];
-        double rr[C], wr[C];
-        auto load_rest = [&](int i0) {
-#pragma unroll
-            for (int k = 0; k < C; k++) {
-                const int i = min(i0 + k, n - 1);
-                xr[k] = x[i];
-                rr[k] = rxp[i];
-                wr[k] = TAB ? wtab[i] : 0.0;
-            }
-        };
-        if (i_rest < n) load_rest(i_rest);
-        for (int i0 = i_rest; i0 < n; i0 += C) {
-            float xc[C];
-            double rc[C], wc[C];
-#pragma unroll
-            for (int k = 0; k < C; k++) { xc[k] = xr[k]; rc[k] = rr[k]; wc[k] = wr[k]; }
-            if (i0 + C < n) load_rest(i0 + C);
-#pragma unroll
-            for (int k = 0; k < C; k++)
-                if (i0 + k < n) pll_step<true, TAB>(r, xc[k], rc[k], Kp, Ki, w, wc[k], tb[i0 + k], pf);
-        }
-    }
-    if (TAB) r.toff = s0.trigOffset + (double)n;               // pll.cpp:46, n times (exact)
-    // every field but lastCarrier (k_nco_out's); the feedback back in the frame of t
-    pllm::rot_q(1u - r.nq1, r.fbI, r.fbQ);
-    st[ch].feedbackI = r.fbI;
-    st[ch].feedbackQ = r.fbQ;
-    st[ch].integrator = r.ip.x;
-    st[ch].phaseEst = r.ip.y;
-    st[ch].trigOffset = r.toff;
-}
-
 // ------------------------------------------------------------------------------------------
-// The PLL step on a LANE PAIR (SPLIT). One lane's step issues ~50 instructions, one per quad-cycle
+// The PLL step on a LANE PAIR. One lane's step issues ~50 instructions, one per quad-cycle
 // for a lone wave, and half of them are the two kernels of cos r and sin r and their roundings and
 // tie keys. Here lanes 2k and 2k+1 both run channel k: the even lane (A) evaluates cos r, the odd
 // lane (B) sin r -- the same instruction stream, f = u + z u P(z) with per-lane coefficients
@@ -432,7 +269,7 @@ __device__ __forceinline__ void pll_run(const PllJob& jb, int n, int ch, const d
 // (A: phaseEst, B: integrator; pll_step_split); the e bracket is proven half on each lane
 // (A: RN32(ed - eps) = e, B: RN32(ed + eps) = e) and each lane proves its own f32 rounding tie, so
 // a chunk is accepted only when both lanes of the pair accept it. A redo runs the full checked
-// step (pll_step<true>) on both lanes of the pair with the exchanged values.
+// step (pll_step_checked) on both lanes of the pair with the exchanged values.
 // ------------------------------------------------------------------------------------------
 struct SplitRegs {
     double f;        // A: cos r, B: sin r (f64)
@@ -616,7 +453,75 @@ __device__ __forceinline__ void gate_wait(InGate& g, int i_end) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 
-// pll_run on lane pairs: ch = channel of the pair, xneg = -x row of the producer (lane A's input).
+// ------------------------------------------------------------------------------------------
+// One lane pair's chain, and its 16-step chunk: what the two feeders of the fast path share
+// (pll_run_split: register prefetch; pll_run_split_coal: LDS-DMA ring). They differ in how a chunk's
+// inputs arrive, how its phases leave, and in their rest loops. (Their prologues and state stores are
+// alike too, but stay written out in each: as shared functions they moved the kernels' instruction
+// streams, profiles/r11/pll_one_path/.)
+// TAB: every lane of the group has the same trigOffset (a context's channels advance together), so
+// w * trigOffset of every step comes from a table the group builds in LDS up front (pll.cpp:46-47
+// evaluated once per step index instead of once per channel and step).
+// ------------------------------------------------------------------------------------------
+struct PairChain {
+    SplitLane L;
+    float Kp, Ki;          // loop-filter gains, for the checked step (L.K holds this lane's own)
+    double w;              // 2 pi freq / Fs
+    SplitRegs r;           // the recurrence's state between chunks
+};
+
+// The chunk at sample i0: 16 fast steps from xb (this lane's input: -x on the even lane) and rb, then
+// the pair's verdict; a chunk either lane cannot prove is redone from its snapshot with the checked
+// step. Touches no global memory: the 16 phases are left in tv.
+template <bool TAB>
+__device__ __forceinline__ void pair_chunk(PairChain& p, const float (&xb)[PLL_CHUNK], const double (&rb)[PLL_CHUNK],
+                                           const double* wtab, int i0, float (&tv)[PLL_CHUNK]) {
+    constexpr int C = PLL_CHUNK;
+    const SplitLane& L = p.L;
+    double wv[C];
+    if (TAB) {
+#pragma unroll
+        for (int k = 0; k < C / 2; k++) {
+            const double2 v = reinterpret_cast<const double2*>(wtab + i0)[k];
+            wv[2 * k] = v.x; wv[2 * k + 1] = v.y;
+        }
+    }
+    const SplitRegs snap = p.r;
+    PllProof pf;
+#pragma unroll
+    for (int j = 0; j < C; j++) pll_step_split<TAB>(p.r, xb[j], rb[j], p.w, TAB ? wv[j] : 0.0, tv[j], pf, L);
+    // this lane's proof: its half of the e bracket, the e range, its own rounding ties, and
+    // the state range (a NaN from an invalid input fails it)
+    const bool ok = (pf.emaxf < PLL_EMAX_F) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
+                    (__builtin_fabs(p.r.s) < L.smax) & (TAB || (pf.tmax < 0x1p30f));
+#if SDR_PLL_COUNT
+    pll_count_chunk(ok);
+    pll_count_reasons(!(pf.emaxf < PLL_EMAX_F), pf.split != 0u, !(pf.tie > pllm::TIE_MIN),
+                      !(__builtin_fabs(p.r.s) < L.smax));
+#endif
+    // the partner's verdict, read with every lane of the pair active (under `ok && ...` the
+    // exchange would sit in a branch, and a lane reading a disabled partner keeps its own value)
+    const int ok_partner = __builtin_amdgcn_mov_dpp((int)ok, 0xB1, 0xF, 0xF, false);
+    const bool pair_ok = ok & (ok_partner != 0);
+    if (!pair_ok) {
+        PllRegs full = split_to_full(snap, L.a);
+#pragma unroll
+        for (int j = 0; j < C; j++)
+            pll_step_checked<TAB>(full, L.a ? -xb[j] : xb[j], rb[j], p.Kp, p.Ki, p.w, TAB ? wv[j] : 0.0, tv[j]);
+        p.r = full_to_split(full, L.a);
+    }
+}
+
+// The register-prefetch feeder (one wave per CU: the headline). ch = channel of the pair; xs: this
+// lane's input row, the producer's -x row on the even lane.
+// VEC: x / rx rows and the t buffer are 16-byte aligned with strides that are multiples of 4
+// (x, t) and 2 (rx), so a chunk's inputs are prefetched with 16-byte loads and the 16 phases are
+// stored with 16-byte stores.
+// Chunks rotate through PLL_NBUF register buffers: chunk c computes from buffer c % NBUF, stores
+// its phases, then refills that buffer with chunk c + NBUF. A chunk's inputs are thus loaded
+// NBUF - 1 chunks ahead and, being issued after the previous chunk's stores, never make a
+// wait include those stores (vmcnt counts loads and stores in issue order). The main loop
+// covers a multiple of NBUF chunks; the rest (< NBUF chunks + n % CHUNK) runs checked steps.
 // GATE: the input arrives in parts (*gate); a separate instantiation, so the blocks that need no
 // gate run the loop without its checks
 template <bool VEC, bool TAB, bool GATE = false>
@@ -627,17 +532,20 @@ __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, c
     const float freq = jb.freq, Fs = jb.Fs, normBandwidth = jb.bw;
     const float Cp = 2.666;
     const float Ci = 3.555;
-    const float Kp = normBandwidth * Cp;
-    const float Ki = normBandwidth * normBandwidth * Ci;
-    const SplitLane L = split_lane(Kp, Ki);
-    const double w = 2 * 3.14159265358979323846 * (freq / Fs);
+    // (filled member by member, ahead of the state load: the order the compiler schedules from)
+    PairChain chain;
+    chain.Kp = normBandwidth * Cp;
+    chain.Ki = normBandwidth * normBandwidth * Ci;
+    chain.L = split_lane(chain.Kp, chain.Ki);
+    chain.w = 2 * 3.14159265358979323846 * (freq / Fs);
+    const SplitLane& L = chain.L;
     const sdr_pll_state s0 = st[ch];
     const float* xpos = jb.in + (size_t)ch * in_stride;
     const float* xs = L.a ? jb.in_neg + (size_t)ch * jb.neg_stride : xpos;   // lane A: -x
     const double* rxp = jb.rx + (size_t)ch * jb.rx_stride;
     float* tb = jb.tbuf + (size_t)ch * t_stride;
     if (!jb.prev_out && L.a) jb.out[(size_t)ch * out_stride] = s0.lastCarrier;   // pll.cpp:18
-    SplitRegs r = full_to_split(pll_load(s0, w), L.a);
+    chain.r = full_to_split(pll_load(s0, chain.w), L.a);
     constexpr int C = PLL_CHUNK, NB = PLL_NBUF;
     const int nchunks = n / C;
     const int nmain = nchunks - nchunks % NB;
@@ -672,41 +580,8 @@ __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, c
 #pragma unroll
         for (int u = 0; u < NB; u++) {
             const int i0 = (c0 + u) * C;
-            double wv[C];
-            if (TAB) {
-#pragma unroll
-                for (int k = 0; k < C / 2; k++) {
-                    const double2 v = reinterpret_cast<const double2*>(wtab + i0)[k];
-                    wv[2 * k] = v.x; wv[2 * k + 1] = v.y;
-                }
-            }
-            const SplitRegs snap = r;
-            PllProof pf;
             float tv[C];
-#pragma unroll
-            for (int j = 0; j < C; j++)
-                pll_step_split<TAB>(r, xb[u][j], rb[u][j], w, TAB ? wv[j] : 0.0, tv[j], pf, L);
-            // this lane's proof: its half of the e bracket, the e range, its own rounding ties, and
-            // the state range (a NaN from an invalid input fails it)
-            const bool ok = (pf.emaxf < PLL_EMAX_F) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
-                            (__builtin_fabs(r.s) < L.smax) & (TAB || (pf.tmax < 0x1p30f));
-#if SDR_PLL_COUNT
-            pll_count_chunk(ok);
-            pll_count_reasons(!(pf.emaxf < PLL_EMAX_F), pf.split != 0u, !(pf.tie > pllm::TIE_MIN),
-                              !(__builtin_fabs(r.s) < L.smax));
-#endif
-            // the partner's verdict, read with every lane of the pair active (under `ok && ...` the
-            // exchange would sit in a branch, and a lane reading a disabled partner keeps its own value)
-            const int ok_partner = __builtin_amdgcn_mov_dpp((int)ok, 0xB1, 0xF, 0xF, false);
-            const bool pair_ok = ok & (ok_partner != 0);
-            if (!pair_ok) {
-                PllRegs full = split_to_full(snap, L.a);
-#pragma unroll
-                for (int j = 0; j < C; j++)
-                    pll_step<true, TAB>(full, L.a ? -xb[u][j] : xb[u][j], rb[u][j], Kp, Ki, w, TAB ? wv[j] : 0.0,
-                                        tv[j], pf);
-                r = full_to_split(full, L.a);
-            }
+            pair_chunk<TAB>(chain, xb[u], rb[u], wtab, i0, tv);
             if (VEC) {
 #pragma unroll
                 for (int k = 0; k < C / 4; k++)
@@ -719,10 +594,11 @@ __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, c
             load_chunk(xb[u], rb[u], min(c0 + u + NB, nmain - 1) * C);
         }
     }
-    PllRegs full = split_to_full(r, L.a);
+    PllRegs full = split_to_full(chain.r, L.a);
     {
-        // the rest (< NB chunks + n % C steps): full checked steps on both lanes of the pair
-        PllProof pf;
+        // the rest (< NB chunks + n % C steps): full checked steps on both lanes of the pair, from
+        // register buffers loaded one piece ahead (one exposed memory latency for the whole rest
+        // instead of one per step)
         const int i_rest = nmain * C;
         float xr[C];
         double rr[C], wr[C];
@@ -745,7 +621,7 @@ __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, c
             if (i0 + C < n) load_rest(i0 + C);
 #pragma unroll
             for (int k = 0; k < C; k++)
-                if (i0 + k < n) pll_step<true, TAB>(full, xc[k], rc[k], Kp, Ki, w, wc[k], tb[i0 + k], pf);
+                if (i0 + k < n) pll_step_checked<TAB>(full, xc[k], rc[k], chain.Kp, chain.Ki, chain.w, wc[k], tb[i0 + k]);
         }
     }
     if (TAB) full.toff = s0.trigOffset + (double)n;            // pll.cpp:46, n times (exact)
@@ -783,10 +659,11 @@ constexpr int COAL_BUF = 6 * COAL_PIECE;              // pieces 0-1: x rows, 2-5
 constexpr int COAL_RING = 3;
 constexpr int COAL_TROW = 80;                         // t staging: 32 rows of 64 B at an 80-byte pitch
 
-template <bool TAB, bool GATE>
+// (never on the fill block, whose input arrives in parts: k_pll_multi runs that one through
+// pll_run_split's gate)
+template <bool TAB>
 __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int ch, const double* __restrict__ wtab,
-                                                   InGate* gate, uint8_t* __restrict__ lbuf,
-                                                   uint8_t* __restrict__ ltst) {
+                                                   uint8_t* __restrict__ lbuf, uint8_t* __restrict__ ltst) {
     const int lane = threadIdx.x & 63;
     const int chw0 = ch - (lane >> 1);                 // the wave's first channel
     const size_t t_stride = jb.t_stride, out_stride = jb.out_stride;
@@ -794,16 +671,18 @@ __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int 
     const float freq = jb.freq, Fs = jb.Fs, normBandwidth = jb.bw;
     const float Cp = 2.666;
     const float Ci = 3.555;
-    const float Kp = normBandwidth * Cp;
-    const float Ki = normBandwidth * normBandwidth * Ci;
-    const SplitLane L = split_lane(Kp, Ki);
-    const double w = 2 * 3.14159265358979323846 * (freq / Fs);
+    PairChain chain;
+    chain.Kp = normBandwidth * Cp;
+    chain.Ki = normBandwidth * normBandwidth * Ci;
+    chain.L = split_lane(chain.Kp, chain.Ki);
+    chain.w = 2 * 3.14159265358979323846 * (freq / Fs);
+    const SplitLane& L = chain.L;
     const sdr_pll_state s0 = st[ch];
     const float* xpos = jb.in + (size_t)ch * jb.in_stride;
     const double* rxp = jb.rx + (size_t)ch * jb.rx_stride;
     float* tb = jb.tbuf + (size_t)ch * t_stride;
     if (!jb.prev_out && L.a) jb.out[(size_t)ch * out_stride] = s0.lastCarrier;   // pll.cpp:18
-    SplitRegs r = full_to_split(pll_load(s0, w), L.a);
+    chain.r = full_to_split(pll_load(s0, chain.w), L.a);
     constexpr int C = PLL_CHUNK;
     static_assert(C == 16, "COAL pieces: 16 samples per row and chunk");
     const int nchunks = n / C;
@@ -858,7 +737,6 @@ __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int 
             rb[2 * p] = v.x; rb[2 * p + 1] = v.y;
         }
     };
-    static_assert(!GATE, "COAL: not on the fill block (its input arrives in parts)");
     if (nmain > 0) {
         issue(0, 0);
         issue(1, min(1, nmain - 1) * C);
@@ -871,31 +749,8 @@ __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int 
         for (int u = 0; u < 2; u++) {
             const int c = c0 + u, i0 = c * C;
             const int bn = bc + 1 == COAL_RING ? 0 : bc + 1;   // buffer of chunk c + 1
-            double wv[C];
-            if (TAB) {
-#pragma unroll
-                for (int k = 0; k < C / 2; k++) {
-                    const double2 v = reinterpret_cast<const double2*>(wtab + i0)[k];
-                    wv[2 * k] = v.x; wv[2 * k + 1] = v.y;
-                }
-            }
-            const SplitRegs snap = r;
-            PllProof pf;
             float tv[C];
-#pragma unroll
-            for (int j = 0; j < C; j++)
-                pll_step_split<TAB>(r, xb[j], rb[j], w, TAB ? wv[j] : 0.0, tv[j], pf, L);
-            const bool ok = (pf.emaxf < PLL_EMAX_F) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
-                            (__builtin_fabs(r.s) < L.smax) & (TAB || (pf.tmax < 0x1p30f));
-            const int ok_partner = __builtin_amdgcn_mov_dpp((int)ok, 0xB1, 0xF, 0xF, false);
-            const bool pair_ok = ok & (ok_partner != 0);
-            if (!pair_ok) {
-                PllRegs full = split_to_full(snap, L.a);
-#pragma unroll
-                for (int j = 0; j < C; j++)
-                    pll_step<true, TAB>(full, L.a ? -xb[j] : xb[j], rb[j], Kp, Ki, w, TAB ? wv[j] : 0.0, tv[j], pf);
-                r = full_to_split(full, L.a);
-            }
+            pair_chunk<TAB>(chain, xb, rb, wtab, i0, tv);
             // the next chunk's rows (its DMA went out a chunk ago), then this chunk's phases out: the
             // even lanes' rows (both lanes of a pair hold the same phases) into LDS, line-shaped
             // pieces back: lane l stores 16 B of channel row 16 k + l / 4
@@ -917,15 +772,10 @@ __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int 
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // spare pieces land before the buffers are reused
-    PllRegs full = split_to_full(r, L.a);
-    {
-        // the rest (< 2 chunks + n % C steps): full checked steps on both lanes of the pair
-        PllProof pf;
-        const int i_rest = nmain * C;
-        if (GATE) gate_wait(*gate, n);
-        for (int i = i_rest; i < n; i++)
-            pll_step<true, TAB>(full, xpos[i], rxp[i], Kp, Ki, w, TAB ? wtab[i] : 0.0, tb[i], pf);
-    }
+    PllRegs full = split_to_full(chain.r, L.a);
+    // the rest (< 2 chunks + n % C steps): full checked steps on both lanes of the pair
+    for (int i = nmain * C; i < n; i++)
+        pll_step_checked<TAB>(full, xpos[i], rxp[i], chain.Kp, chain.Ki, chain.w, TAB ? wtab[i] : 0.0, tb[i]);
     if (TAB) full.toff = s0.trigOffset + (double)n;            // pll.cpp:46, n times (exact)
     if (L.a) {   // every field but lastCarrier (the NCO's); the feedback back in the frame of t
         pllm::rot_q(1u - full.nq1, full.fbI, full.fbQ);
@@ -941,12 +791,12 @@ __device__ __forceinline__ void pll_run_split_coal(const PllJob& jb, int n, int 
 // (x, t) and 2 (rx), so a chunk's inputs are prefetched with 16-byte loads and the 16 phases are
 // stored with 16-byte stores -- the unrolled chunk itself touches no memory.
 // Dynamic LDS: n doubles when the launch allows the trigArg table (launch_plls), else none.
-// SPLIT: two lanes per channel (pll_run_split), else one.
-template <bool VEC, bool SPLIT>
+// Two lanes per channel (pll_run_split).
+template <bool VEC>
 __global__ __launch_bounds__(64) void k_pll(const PllJobs jobs, int n, int nch, int tab_ok) {
     extern __shared__ double wtab[];
     const int lg = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ch = SPLIT ? lg >> 1 : lg;                    // lane 0 always holds a channel
+    const int ch = lg >> 1;                                 // lane 0 always holds a channel
     const bool active = ch < nch;
     const PllJob& jb = jobs.j[blockIdx.y];
     // the serial PLL bounds every block-step: let its waves win issue arbitration on shared SIMDs
@@ -967,13 +817,8 @@ __global__ __launch_bounds__(64) void k_pll(const PllJobs jobs, int n, int nch, 
 #if SDR_PLL_HWID
     const unsigned long long hw_c0 = __builtin_amdgcn_s_memtime(), hw_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    if (SPLIT) {
-        if (tab) pll_run_split<VEC, true>(jb, n, ch, wtab);
-        else pll_run_split<VEC, false>(jb, n, ch, nullptr);
-    } else {
-        if (tab) pll_run<VEC, true>(jb, n, ch, wtab);
-        else pll_run<VEC, false>(jb, n, ch, nullptr);
-    }
+    if (tab) pll_run_split<VEC, true>(jb, n, ch, wtab);
+    else pll_run_split<VEC, false>(jb, n, ch, nullptr);
 #if SDR_PLL_HWID
     const unsigned long long hw_c1 = __builtin_amdgcn_s_memtime(), hw_r1 = __builtin_amdgcn_s_memrealtime();
     uint32_t hw_id, xcc_id;
@@ -1009,14 +854,15 @@ __global__ __launch_bounds__(64) void k_pll(const PllJobs jobs, int n, int nch, 
 // LDS (all channels of a context advance together, so one table serves every wave whose lanes share
 // the group's trigOffset), its wave 0 polls the block flag, and two barriers per block keep the
 // group's waves on the same block (the table is rebuilt only after every wave finished reading it).
-template <bool VEC, bool SPLIT, int WG, bool COAL = false>
+// The rows of a persistent job are always 16-byte aligned (pll_multi_plan refuses others), so the
+// lane-pair loop is the 16-byte (VEC) form; COAL: the packed groups' LDS-staged loop.
+template <int WG, bool COAL = false>
 __global__ __launch_bounds__(64 * WG) void k_pll_multi(const PllJobs2 jobs, int n, int nch, int tab_ok, int nblocks,
                                                        const uint32_t* pre_flag, uint32_t pre_first,
                                                        uint32_t* done_ring, uint32_t* err,
                                                        unsigned long long* t_start, unsigned long long* t_end,
                                                        unsigned long long* t_cyc, const uint32_t* sub_flag,
                                                        uint32_t sub_base, int sub_tile) {
-    static_assert(!COAL || (VEC && SPLIT), "COAL: the lane-pair loop with 16-byte rows");
     extern __shared__ double wtab[];
     __shared__ double sh_toff;
     __shared__ int sh_dead;
@@ -1027,7 +873,7 @@ __global__ __launch_bounds__(64 * WG) void k_pll_multi(const PllJobs2 jobs, int 
     uint8_t* const my_buf = coal_buf + (COAL ? (threadIdx.x >> 6) * COAL_RING * COAL_BUF : 0);
     uint8_t* const my_tst = coal_tst + (COAL ? (threadIdx.x >> 6) * 32 * COAL_TROW : 0);
     const int lg = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ch = SPLIT ? lg >> 1 : lg;
+    const int ch = lg >> 1;
     const bool active = ch < nch;
     const bool lane0 = (threadIdx.x & 63) == 0;
     __builtin_amdgcn_s_setprio(3);
@@ -1040,9 +886,9 @@ __global__ __launch_bounds__(64 * WG) void k_pll_multi(const PllJobs2 jobs, int 
         const PllJob& jb = jobs.p[j & 1].j[blockIdx.y];   // p[0]: the parity of the launch's first block
         const uint32_t want = pre_first + (uint32_t)j + 1u;
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        // the first block may start on its first published part (SPLIT: the lane-pair PLL gates its
-        // loads, InGate)
-        const bool parts = SPLIT && j == 0 && sub_flag != nullptr;
+        // the first block may start on its first published part (the lane-pair loop gates its loads,
+        // InGate)
+        const bool parts = j == 0 && sub_flag != nullptr;
         if (!dead) {
             // poll with relaxed loads and acquire once: an acquire load at agent scope invalidates
             // the wave's caches (on a multi-XCD device its XCD's L2) on every poll, which slowed the
@@ -1103,22 +949,17 @@ __global__ __launch_bounds__(64 * WG) void k_pll_multi(const PllJobs2 jobs, int 
             __syncthreads();
             const bool tab = group_tab && __all(!active || toff0 == toff_g);
             if (active) {
-                if (SPLIT) {
-                    if (parts) {
-                        InGate g{pre_flag, sub_flag, err, want, sub_base, sub_tile, n, 0, t0};
-                        gate_wait(g, 1);      // the part(s) the wait above saw
-                        if (tab) pll_run_split<VEC, true, true>(jb, n, ch, wtab, &g);
-                        else pll_run_split<VEC, false, true>(jb, n, ch, nullptr, &g);
-                    } else if constexpr (COAL) {
-                        if (tab) pll_run_split_coal<true, false>(jb, n, ch, wtab, nullptr, my_buf, my_tst);
-                        else pll_run_split_coal<false, false>(jb, n, ch, nullptr, nullptr, my_buf, my_tst);
-                    } else {
-                        if (tab) pll_run_split<VEC, true>(jb, n, ch, wtab);
-                        else pll_run_split<VEC, false>(jb, n, ch, nullptr);
-                    }
+                if (parts) {
+                    InGate g{pre_flag, sub_flag, err, want, sub_base, sub_tile, n, 0, t0};
+                    gate_wait(g, 1);      // the part(s) the wait above saw
+                    if (tab) pll_run_split<true, true, true>(jb, n, ch, wtab, &g);
+                    else pll_run_split<true, false, true>(jb, n, ch, nullptr, &g);
+                } else if constexpr (COAL) {
+                    if (tab) pll_run_split_coal<true>(jb, n, ch, wtab, my_buf, my_tst);
+                    else pll_run_split_coal<false>(jb, n, ch, nullptr, my_buf, my_tst);
                 } else {
-                    if (tab) pll_run<VEC, true>(jb, n, ch, wtab);
-                    else pll_run<VEC, false>(jb, n, ch, nullptr);
+                    if (tab) pll_run_split<true, true>(jb, n, ch, wtab);
+                    else pll_run_split<true, false>(jb, n, ch, nullptr);
                 }
             }
             __syncthreads();   // every lane's table reads and state/phase stores issued before the release
@@ -1266,10 +1107,30 @@ __global__ __launch_bounds__(BLK) void k_nco_out(const PllJobs jobs, int n) {
     if (i == n - 1) st[ch].lastCarrier = v;
     if (i == 0 && jb.prev_out) o[-1] = jb.prev_out[(size_t)ch * out_stride + n];
 }
-// PLL + NCO output: k_pll (fast, default) or k_pll_libm (SDR_FLAG_PLL_LIBM)
-}  // namespace
 
-// compile-time A/B switches for variant builds (tools/build_variant.sh), never read at run time:
+// every row of the job is 16-byte aligned with a stride that keeps it so (x, -x, t: multiples of 4
+// floats; rx: of 2 doubles): the lane-pair loop's VEC form
+bool pll_rows16(const PllJob& j) {
+    return reinterpret_cast<uintptr_t>(j.in) % 16 == 0 && j.in_stride % 4 == 0 &&
+           reinterpret_cast<uintptr_t>(j.tbuf) % 16 == 0 && j.t_stride % 4 == 0 &&
+           reinterpret_cast<uintptr_t>(j.rx) % 16 == 0 && j.rx_stride % 2 == 0 &&
+           reinterpret_cast<uintptr_t>(j.in_neg) % 16 == 0 && j.neg_stride % 4 == 0;
+}
+
+// LDS table of w * trigOffset: n doubles in 16-byte rows, when they fit 64 KiB
+struct PllTab {
+    size_t bytes;
+    int ok;
+    size_t lds;   // dynamic LDS of the launch: bytes, or 0 without the table
+};
+PllTab pll_tab(int n) {
+    PllTab t;
+    t.bytes = round_up((size_t)std::max(n, 1), 2) * sizeof(double);
+    t.ok = t.bytes <= 64 * 1024 ? 1 : 0;
+    t.lds = t.ok ? t.bytes : 0;
+    return t;
+}
+}  // namespace
 
 int launch_nco(const PllJobs& jobs, int njobs, int n, int nch, hipStream_t s) {
     if (n > 0) {
@@ -1280,29 +1141,18 @@ int launch_nco(const PllJobs& jobs, int njobs, int n, int nch, hipStream_t s) {
 }
 
 int launch_plls(bool libm, const PllJobs& jobs, int njobs, int n, int nch, hipStream_t s, bool with_nco) {
-    bool vec = true, split = true;
+    bool vec = true;
     for (int k = 0; k < njobs; k++) {
         const PllJob& j = jobs.j[k];
-        vec = vec && (reinterpret_cast<uintptr_t>(j.in) % 16 == 0) && (j.in_stride % 4 == 0) &&
-              (reinterpret_cast<uintptr_t>(j.tbuf) % 16 == 0) && (j.t_stride % 4 == 0) &&
-              (reinterpret_cast<uintptr_t>(j.rx) % 16 == 0) && (j.rx_stride % 2 == 0) &&
-              (!j.in_neg || (reinterpret_cast<uintptr_t>(j.in_neg) % 16 == 0 && j.neg_stride % 4 == 0));
-        split = split && j.in_neg;   // lane pairs need the producer's -x row
+        if (!j.in_neg || !j.rx) return fail(SDR_E_INVALID, "plls: job %d lacks its -x or reciprocal row", k);
+        vec = vec && pll_rows16(j);
     }
-    const dim3 g(cdiv(split ? 2 * nch : nch, 64), njobs), b(64);
-    // LDS table of w * trigOffset (k_pll): n doubles, 16-byte rows
-    const size_t tab_bytes = round_up((size_t)std::max(n, 1), 2) * sizeof(double);
-    const int tab_ok = tab_bytes <= 64 * 1024 ? 1 : 0;
-    const size_t lds = tab_ok ? tab_bytes : 0;
-    if (libm) {
-        hipLaunchKernelGGL(k_pll_libm, g, b, 0, s, jobs, n, nch);
-    } else if (vec) {
-        if (split) hipLaunchKernelGGL((k_pll<true, true>), g, b, lds, s, jobs, n, nch, tab_ok);
-        else hipLaunchKernelGGL((k_pll<true, false>), g, b, lds, s, jobs, n, nch, tab_ok);
-    } else {
-        if (split) hipLaunchKernelGGL((k_pll<false, true>), g, b, lds, s, jobs, n, nch, tab_ok);
-        else hipLaunchKernelGGL((k_pll<false, false>), g, b, lds, s, jobs, n, nch, tab_ok);
-    }
+    // a lane pair per channel (k_pll_libm runs one lane per channel inside the same grid)
+    const dim3 g(cdiv(2 * nch, 64), njobs), b(64);
+    const PllTab tab = pll_tab(n);
+    if (libm) hipLaunchKernelGGL(k_pll_libm, g, b, 0, s, jobs, n, nch);
+    else if (vec) hipLaunchKernelGGL(k_pll<true>, g, b, tab.lds, s, jobs, n, nch, tab.ok);
+    else hipLaunchKernelGGL(k_pll<false>, g, b, tab.lds, s, jobs, n, nch, tab.ok);
     LAUNCH_CHECK();
     return with_nco ? launch_nco(jobs, njobs, n, nch, s) : SDR_OK;
 }
@@ -1322,39 +1172,27 @@ int launch_pll(bool libm, const float* in, size_t in_stride, int n, int nch, flo
 }
 
 int pll_multi_plan(const PllJobs2& jobs, int njobs, int n, int nch, const CuPlacement& pl, PllMultiPlan* plan) {
-    bool vec = true, split = true;
     for (int k = 0; k < 2; k++)
         for (int q = 0; q < njobs; q++) {
             const PllJob& j = jobs.p[k].j[q];
-            vec = vec && (reinterpret_cast<uintptr_t>(j.in) % 16 == 0) && (j.in_stride % 4 == 0) &&
-                  (reinterpret_cast<uintptr_t>(j.tbuf) % 16 == 0) && (j.t_stride % 4 == 0) &&
-                  (reinterpret_cast<uintptr_t>(j.rx) % 16 == 0) && (j.rx_stride % 2 == 0) &&
-                  (!j.in_neg || (reinterpret_cast<uintptr_t>(j.in_neg) % 16 == 0 && j.neg_stride % 4 == 0));
-            split = split && j.in_neg;
+            if (!j.in_neg || !j.rx || !pll_rows16(j))
+                return fail(SDR_E_INVALID, "plls_launch: job %d of parity %d lacks its -x or reciprocal row, or its "
+                            "rows are not 16-byte aligned", q, k);
         }
     PllMultiPlan& P = *plan;
-    const size_t tab_bytes = round_up((size_t)std::max(n, 1), 2) * sizeof(double);
-    P.tab_ok = tab_bytes <= 64 * 1024 ? 1 : 0;
-    P.lds = P.tab_ok ? tab_bytes : 0;
-    const int wave_cnt = cdiv(split ? 2 * nch : nch, 64) * njobs;
+    const PllTab tab = pll_tab(n);
+    P.tab_ok = tab.ok;
+    P.lds = tab.lds;
+    const int wave_cnt = cdiv(2 * nch, 64) * njobs;
     // one wave per workgroup (its own CU time slice and table) while two tables per CU fit the
     // stream's CUs, else groups of 4 waves -- one per SIMD -- sharing one table per CU
     P.WG = wave_cnt > 2 * pl.ncu ? 4 : 1;
-    P.g = dim3(cdiv(split ? 2 * nch : nch, 64 * P.WG), njobs);
+    P.g = dim3(cdiv(2 * nch, 64 * P.WG), njobs);
     P.b = dim3(64 * P.WG);
     P.waves = P.g.x * P.g.y * P.WG;
     P.groups = (long long)P.g.x * P.g.y;
-    auto kern_of = [&](auto v, auto sp, auto wg) -> const void* {
-        return reinterpret_cast<const void*>(k_pll_multi<decltype(v)::value, decltype(sp)::value, decltype(wg)::value>);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    using W1 = std::integral_constant<int, 1>;
-    using W4 = std::integral_constant<int, 4>;
-    const void* plain = P.WG == 4 ? (vec ? (split ? kern_of(T{}, T{}, W4{}) : kern_of(T{}, F{}, W4{}))
-                                         : (split ? kern_of(F{}, T{}, W4{}) : kern_of(F{}, F{}, W4{})))
-                                  : (vec ? (split ? kern_of(T{}, T{}, W1{}) : kern_of(T{}, F{}, W1{}))
-                                         : (split ? kern_of(F{}, T{}, W1{}) : kern_of(F{}, F{}, W1{})));
+    const void* plain = P.WG == 4 ? reinterpret_cast<const void*>(k_pll_multi<4>)
+                                  : reinterpret_cast<const void*>(k_pll_multi<1>);
     // every workgroup of a persistent launch must be resident at once (a wave that cannot start holds
     // up the done count of every block, and the producer of later blocks waits for that): the
     // workgroups of this kernel that fit one CU (its VGPRs, the LDS table) times what the placement of
@@ -1362,7 +1200,7 @@ int pll_multi_plan(const PllJobs2& jobs, int njobs, int n, int nch, const CuPlac
     auto resident = [&](const void* kern, int* per_cu) {
         *per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 64 * P.WG, P.lds) != hipSuccess || *per_cu <= 0)
-            *per_cu = std::min(4 / P.WG, P.tab_ok ? (int)(160 * 1024 / tab_bytes) : 4 / P.WG);
+            *per_cu = std::min(4 / P.WG, P.tab_ok ? (int)(160 * 1024 / tab.bytes) : 4 / P.WG);
         return pl.resident(*per_cu);
     };
     // packed groups (more than two waves per CU): the chunk inputs and phases through LDS in
@@ -1372,8 +1210,8 @@ int pll_multi_plan(const PllJobs2& jobs, int njobs, int n, int nch, const CuPlac
     // group, beside the table) fits one group per CU: a launch that needs more falls back to the register-prefetch
     // groups, which fit two.
     P.kern = plain;
-    if (vec && split && nch % 32 == 0 && P.WG == 4) {
-        const void* coal = reinterpret_cast<const void*>(k_pll_multi<true, true, 4, true>);
+    if (nch % 32 == 0 && P.WG == 4) {
+        const void* coal = reinterpret_cast<const void*>(k_pll_multi<4, true>);
         int pc = 0;
         const long long r = resident(coal, &pc);
         if (r >= P.groups) {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The lane-pair PLL step's ISA with its dependent chain marked.
 
-Disassembles k_pll_multi<VEC, SPLIT, WG = 1> from a device-only build of sdr_pll.hip, finds the
+Disassembles k_pll_multi<WG = 1, COAL = false> from a device-only build of sdr_pll.hip, finds the
 unrolled fast 16-step chunk of the trigArg-table path (the basic block with 16 v_bitop3_b32, one
 per step), builds the VGPR def-use graph of the chunk (64-bit operands as register pairs, DPP and
 op_sel sources included) and reports:
@@ -62,7 +62,7 @@ def main() -> None:
         dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", str(obj)], capture_output=True, text=True,
                              check=True).stdout
     lines = dis.split("\n")
-    start = next(i for i, l in enumerate(lines) if re.search(r"<.*k_pll_multiILb1ELb1ELi1ELb0E.*>:", l))
+    start = next(i for i, l in enumerate(lines) if re.search(r"<.*k_pll_multiILi1ELb0EE.*>:", l))
     end = next(i for i in range(start + 1, len(lines)) if re.match(r"^[0-9a-f]+ <.*>:$", lines[i].strip()))
     # basic blocks of the kernel; the TAB fast chunk: 16 bitop3 and 8 ds_read_b128 (the table)
     blocks, cur = [], []
@@ -122,7 +122,7 @@ def main() -> None:
     bops = [i for i, x in enumerate(chunk) if x[0] == "v_bitop3_b32"]
     lo, hi = bops[7] + 1, bops[8] + 1
     out = []
-    out.append("k_pll_multi<VEC, SPLIT, WG = 1>, trigArg-table fast chunk (16 unrolled lane-pair steps), "
+    out.append("k_pll_multi<WG = 1>, trigArg-table fast chunk (16 unrolled lane-pair steps), "
                "gfx950, from tools/pll_isa.py")
     out.append("per step: " + ", ".join(f"{k} {v / steps:.2f}" for k, v in cnt.items()))
     out.append("f64 ops per step: " + ", ".join(f"{k} {v / steps:.2f}" for k, v in sorted(f64.items())) +
