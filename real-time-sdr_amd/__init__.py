@@ -143,6 +143,7 @@ def lib() -> C.CDLL:
         "sdr_plls_launch": ([vp, i32, vp], i32),
         "sdr_plls_prepare": ([vp, i32, vp], i32),
         "sdr_plls_fits": ([vp, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], i32),
+        "sdr_diag_plls_plan": ([vp, i32, i32, i32, C.POINTER(i32)], i32),
         "sdr_plls_launch_sel": ([vp, i32, i32, vp], i32),
         "sdr_plls_signal": ([vp, vp], i32),
         "sdr_frontend_pre_parts": ([vp, vp, sz, i32, vp], i32),
@@ -784,6 +785,15 @@ class Pipeline:
         check(lib().sdr_plls_fits(self._h, which, first_cu, n_cu, C.byref(w), C.byref(g), C.byref(r)),
               "sdr_plls_fits")
         return {"waves": w.value, "groups": g.value, "resident": r.value, "fits": g.value <= r.value}
+
+    def plls_plan(self, n_cu: int, first_cu: int = 0, which: int = 3) -> dict:
+        """Which kernel plls_launch(which) takes on a stream over CUs [first_cu, first_cu + n_cu)
+        (sdr_diag_plls_plan; nothing is enqueued): waves per workgroup, whether it is the LDS-staged
+        lane-pair loop, whether the trigArg table fits LDS (the TAB = true kernels), and the
+        launch's dynamic LDS bytes."""
+        out = (C.c_int * 4)()
+        check(lib().sdr_diag_plls_plan(self._h, which, first_cu, n_cu, out), "sdr_diag_plls_plan")
+        return {"wg_waves": out[0], "staged": bool(out[1]), "tab_ok": out[2], "lds": out[3]}
 
     def plls_prepare(self, nblocks: int, stream=None):
         """The launch's bookkeeping ahead of plls_launch(nblocks) (allocation, stamp reset)."""

@@ -158,6 +158,7 @@ CuPlacement cu_placement(const uint32_t* mask, int nwords, int ncu_dev, int nxcc
 struct PllMultiPlan {
     const void* kern = nullptr;
     int WG = 1, tab_ok = 0, per_cu = 0;
+    int staged = 0;         // kern is the LDS-staged lane-pair loop (k_pll_multi<4, true>)
     size_t lds = 0;
     dim3 g, b;
     uint32_t waves = 0;

@@ -2743,25 +2743,45 @@ static int plls_which_ok(const sdr_ctx* c, int which, const char* what) {
     return SDR_OK;
 }
 
-int sdr_plls_fits(sdr_ctx* c, int which, int first_cu, int n_cu, int* waves, long long* groups, long long* resident) {
-    if (!c || !waves || !groups || !resident) return fail(SDR_E_INVALID, "plls_fits: bad arguments");
-    if (const int r = plls_which_ok(c, which, "plls_fits")) return r;
+// the plan of a persistent launch of `which` on a stream over CUs [first_cu, first_cu + n_cu)
+static int plls_plan_on(sdr_ctx* c, int which, int first_cu, int n_cu, const char* what, PllMultiPlan* P) {
+    if (const int r = plls_which_ok(c, which, what)) return r;
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, c->device));
     const int ncu = prop.multiProcessorCount;
     if (first_cu < 0 || n_cu <= 0 || first_cu + n_cu > ncu)
-        return fail(SDR_E_INVALID, "plls_fits: CUs [%d, %d) outside [0, %d)", first_cu, first_cu + n_cu, ncu);
+        return fail(SDR_E_INVALID, "%s: CUs [%d, %d) outside [0, %d)", what, first_cu, first_cu + n_cu, ncu);
     int nset = 0;
     const std::vector<uint32_t> mask = cu_range_mask(ncu, first_cu, n_cu, 0, &nset);
     const CuPlacement pl = cu_placement(mask.data(), (int)mask.size(), ncu, device_xccs(c->device));
     HIP_TRY(hipSetDevice(c->device));
     int njobs = 0;
     const PllJobs2 jobs = plls_jobs(c, which, &njobs);
+    return pll_multi_plan(jobs, njobs, c->info.block_if, c->nch, pl, P);
+}
+
+int sdr_plls_fits(sdr_ctx* c, int which, int first_cu, int n_cu, int* waves, long long* groups, long long* resident) {
+    if (!c || !waves || !groups || !resident) return fail(SDR_E_INVALID, "plls_fits: bad arguments");
     PllMultiPlan P;
-    if (const int r = pll_multi_plan(jobs, njobs, c->info.block_if, c->nch, pl, &P)) return r;
+    if (const int r = plls_plan_on(c, which, first_cu, n_cu, "plls_fits", &P)) return r;
     *waves = (int)P.waves;
     *groups = P.groups;
     *resident = P.resident;
+    return SDR_OK;
+}
+
+// Diagnosis (not part of sdr_amd.h): which kernel sdr_plls_launch_sel(which) takes on a stream over CUs
+// [first_cu, first_cu + n_cu). out = [waves per workgroup, 1: the LDS-staged loop (pll_run_split_coal),
+// 1: the trigArg table fits LDS (TAB = true until w * trigOffset passes PLL_TAB_WT_MAX), dynamic LDS
+// bytes]. Nothing is enqueued.
+int sdr_diag_plls_plan(sdr_ctx* c, int which, int first_cu, int n_cu, int out[4]) {
+    if (!c || !out) return fail(SDR_E_INVALID, "diag_plls_plan: bad arguments");
+    PllMultiPlan P;
+    if (const int r = plls_plan_on(c, which, first_cu, n_cu, "diag_plls_plan", &P)) return r;
+    out[0] = P.WG;
+    out[1] = P.staged;
+    out[2] = P.tab_ok;
+    out[3] = (int)P.lds;
     return SDR_OK;
 }
 

@@ -1210,12 +1210,14 @@ int pll_multi_plan(const PllJobs2& jobs, int njobs, int n, int nch, const CuPlac
     // group, beside the table) fits one group per CU: a launch that needs more falls back to the register-prefetch
     // groups, which fit two.
     P.kern = plain;
+    P.staged = 0;
     if (nch % 32 == 0 && P.WG == 4) {
         const void* coal = reinterpret_cast<const void*>(k_pll_multi<4, true>);
         int pc = 0;
         const long long r = resident(coal, &pc);
         if (r >= P.groups) {
             P.kern = coal;
+            P.staged = 1;
             P.per_cu = pc;
             P.resident = r;
             return SDR_OK;

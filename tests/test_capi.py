@@ -61,6 +61,15 @@ def test_diagnosis_counters_absent_in_product_build(pkg):
     assert pkg.lib().sdr_diag_pll_hwid(hwid, 4) == -1
 
 
+def test_plls_plan_diagnostic_is_exported_outside_the_header(pkg):
+    """sdr_diag_plls_plan (Pipeline.plls_plan: which PLL kernel a persistent launch takes) is a
+    diagnostic entry, not part of sdr_amd.h; it rejects NULL arguments without touching a GPU."""
+    assert "sdr_diag_plls_plan" not in _declared("sdr_amd.h")
+    out = (C.c_int * 4)()
+    assert pkg.lib().sdr_diag_plls_plan(None, 3, 0, 8, out) == -1
+    assert b"diag_plls_plan" in pkg.lib().sdr_last_error()
+
+
 def test_product_taps_equal_reference_taps(pkg, golden):
     cases = {
         "rf": pkg.impulse_response_lpf(2.4e6, 1e5, 101),

@@ -114,7 +114,13 @@ def test_pipeline_many_channels_vs_oracle(pkg, synth, oracle, torch_cuda, row_al
 
 @pytest.mark.parametrize("mode", [1, 2, 3])
 def test_other_modes_vs_oracle(pkg, synth, oracle, torch_cuda, mode):
-    """Modes 1-3 (project.cpp:76-103): other decimations and the 147/800, 147/1280 resamplers."""
+    """Modes 1-3 (project.cpp:76-103): other decimations and the 147/800, 147/1280 resamplers, one
+    channel on one stream, pinned to the unmodified reference (golden_modes123.json): the only tie of
+    these modes to it. The input is the 2.4 MS/s multiplex of FMMultiplexSource whatever the mode, so
+    modes 1 and 3 read it at 1.44 and 1.152 MS/s: the pilot lands near 11.4 and 9.1 kHz, outside the
+    pilot band-pass, and both PLLs run on filter noise (tests/test_synth_rates.py shows it). The
+    fixture was recorded on these bytes, so they stay; the right-rate inputs, more channels, the
+    hostile kinds and the bench's schedules are tests/test_gpu_modes.py."""
     import real_time_sdr_amd.synth as s
     ch = oracle.Channel(mode, True)
     nb = 7
