@@ -13,7 +13,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-g
             -Wall -Iinclude
 LIB      := $(PKG)/libsdr_amd.so
 SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_scan.hip \
-            $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip \
+            $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip $(PKG)/csrc/sdr_split.hip \
             $(PKG)/csrc/sdr_taps.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
 HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h
@@ -23,9 +23,11 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -pthread -D__HIP_PLATFORM_AMD__ 
              -Iinclude -Iinclude/dropin -I$(PKG)/host
 HOSTLIB   := $(PKG)/libsdr_host.so
 HOSTSRCS  := $(PKG)/host/dropin_primitives.cpp $(PKG)/host/dropin_stages.cpp $(PKG)/host/rds_frame.cpp \
-             $(PKG)/host/sdr_multi_engine.cpp $(PKG)/host/sdr_scan_run.cpp
+             $(PKG)/host/sdr_multi_engine.cpp $(PKG)/host/sdr_scan_run.cpp \
+             $(PKG)/host/sdr_wide_scan.cpp
 HOSTHDRS  := $(wildcard include/dropin/*.h) $(PKG)/host/hip_util.h include/sdr_amd.h include/sdr_multi.h \
-             include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h
+             include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h \
+             include/sdr_multi_wide.h include/sdr_wide_scan.h
 CLI       := $(PKG)/bin/sdr_project
 MULTI     := $(PKG)/bin/sdr_multi
 
@@ -64,7 +66,7 @@ $(CLI): $(PKG)/host/sdr_project.cpp $(HOSTLIB)
 	@mkdir -p $(dir $@)
 	$(CXX) $(HOSTFLAGS) -o $@ $< -L$(PKG) -lsdr_host -Wl,-rpath,'$$ORIGIN/..'
 
-$(MULTI): $(PKG)/host/sdr_multi.cpp include/sdr_multi.h include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h $(HOSTLIB)
+$(MULTI): $(PKG)/host/sdr_multi.cpp include/sdr_multi.h include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h include/sdr_multi_wide.h include/sdr_wide_scan.h $(HOSTLIB)
 	@mkdir -p $(dir $@)
 	$(CXX) $(HOSTFLAGS) -o $@ $< -L$(PKG) -lsdr_host -lsdr_amd -L$(ROCM)/lib -lamdhip64 \
 	    -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,$(ROCM)/lib

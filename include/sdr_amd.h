@@ -227,6 +227,51 @@ int sdr_scan_block(sdr_scan *s, const uint8_t *iq, size_t iq_stride, void *strea
 /* psd: host [nsrc][N]; *segments = S per row (psd is all zero while S = 0); synchronises `stream` */
 int sdr_scan_psd(sdr_scan *s, float *psd, long long *segments, void *stream);
 
+/* ---- wideband splitter (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
+ * one wide signed 8-bit I/Q capture at W * rf_Fs (W = 4, 8 or 10; a HackRF's 19.2 MS/s is W = 8 in mode 0)
+ * into the R = 2 W - 1 half-overlapping u8 capture rows at rf_Fs that sdr_frontend_tuned and
+ * sdr_scan_block read. With N = rf_Fs / 1000, row r has k = r - (W - 1) and its centre k N / 2 kHz off the
+ * wide capture's centre: a station at F = k N / 2 + d kHz of the wide capture is the station khz = +d of
+ * row r, and every station lies within N / 4 of some row's centre. All integer, so every correct
+ * implementation gives the same bytes.
+ *   input    [nwide][2 W block_iq] int8, I then Q; x[n] = sample n of a stream counted from the last
+ *            reset, x[n] = 0 for n < 0 (the handle carries the last T - 1 samples from block to block)
+ *   taps     T = 16 W, int16 g[r][m] = (g_re, g_im), in f64 and rounded to nearest (rint):
+ *                u = m - (T - 1) / 2,  sinc(x) = sin(pi x) / (pi x)
+ *                h = sinc(u / W) (0.42 - 0.5 cos(2 pi (m + 1/2) / T) + 0.08 cos(4 pi (m + 1/2) / T))
+ *                theta = pi ((k (2 m - T + 1)) mod 4 W) / (2 W)      (the integer reduced first, to [0, 4 W))
+ *                g_re = rint(8191 h cos theta),  g_im = rint(8191 h sin theta)
+ *            (flat within 0.01 dB to N / 4 + 128 kHz of the row's centre, aliases into that region at
+ *            least 71 dB down, max |g| = 8156)
+ *   output   sample t (absolute: block * block_iq + index) of row r, in int32 (|acc| < 2.4e8):
+ *                acc_re = sum_m g_re[m] x_I[W t - m] - g_im[m] x_Q[W t - m]
+ *                acc_im = sum_m g_re[m] x_Q[W t - m] + g_im[m] x_I[W t - m]
+ *                if k t is odd: acc = -acc            (the row lands at 0 Hz, not at rf_Fs / 2)
+ *                v = 128 + ((acc + (1 << (shift - 1))) >> shift)    (arithmetic shift)
+ *                out = clamp(v, 0, 255); each component with v < 0 or v > 255 adds 1 to clips[stream][r]
+ *            shift in 1..24, default 14, 15, 16 for W = 4, 8, 10 (DC gain 2.0, 2.0, 1.25).
+ *   rows     output row w R + r is stream w, row r: u8 I/Q, 2 block_iq bytes, row_stride apart.
+ *
+ * host only, no GPU (any output pointer may be NULL): rows = R, taps = T, wide_iq = W block_iq,
+ * half_khz = N / 2 (the spacing of the row centres), shift_default */
+typedef struct sdr_split sdr_split;
+int sdr_split_geometry(int mode, int W, int *rows, int *taps, int *wide_iq, int *half_khz, int *shift_default);
+/* the tap table: *n = R T, g = [R][T][2] filled when g != NULL and max_pairs >= R T */
+int sdr_split_taps(int W, int16_t *g, int max_pairs, int *n);
+/* device: the splitter is its own handle (no sdr_ctx); it may run on any stream beside a running
+ * pipeline. shift <= 0 takes the default. SDR_E_INVALID, with nothing enqueued, for a bad mode, W, nwide
+ * (1..4096) or shift, NULL pointers, wide_stride < 2 W block_iq or no multiple of 4, wide not 4-byte
+ * aligned, or a rows / row_stride that sdr_frontend_tuned would refuse (row_stride >= 2 block_iq, both
+ * even; 4-byte aligned rows are stored in whole dwords). */
+int sdr_split_create(sdr_split **out, int device, int mode, int W, int nwide, int shift);
+int sdr_split_destroy(sdr_split *s);
+int sdr_split_reset(sdr_split *s, void *stream);     /* history and clip counters back to 0 */
+/* one block of every stream: one launch on `stream`, no sync */
+int sdr_split_block(sdr_split *s, const int8_t *wide, size_t wide_stride, uint8_t *rows, size_t row_stride,
+                    void *stream);
+/* clips: host [nwide * R], accumulated since the last reset; synchronises `stream` */
+int sdr_split_clips(sdr_split *s, long long *clips, void *stream);
+
 /* ---- reception meter (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
  * per channel and block, what a receiver's stereo lamp and tuning indicator show, reduced on the GPU
  * from rows the pipeline already keeps. n = block_if, x = the block's fm_demod row, x[-100..-1] the

@@ -164,6 +164,13 @@ def lib() -> C.CDLL:
         "sdr_scan_reset": ([vp, vp], i32),
         "sdr_scan_block": ([vp, vp, sz, vp], i32),
         "sdr_scan_psd": ([vp, vp, C.POINTER(C.c_longlong), vp], i32),
+        "sdr_split_geometry": ([i32, i32] + [C.POINTER(i32)] * 5, i32),
+        "sdr_split_taps": ([i32, vp, i32, C.POINTER(i32)], i32),
+        "sdr_split_create": ([C.POINTER(vp), i32, i32, i32, i32, i32], i32),
+        "sdr_split_destroy": ([vp], i32),
+        "sdr_split_reset": ([vp, vp], i32),
+        "sdr_split_block": ([vp, vp, sz, vp, sz, vp], i32),
+        "sdr_split_clips": ([vp, vp, vp], i32),
         "sdr_meter_taps": ([i32, vp, i32, C.POINTER(i32)], i32),
         "sdr_meter_opts_default": ([C.POINTER(MeterOpts)], None),
         "sdr_meter_status": ([i32, C.POINTER(MeterRow), C.POINTER(MeterOpts), C.POINTER(MeterState)], i32),
@@ -371,6 +378,76 @@ class Scanner:
             src.append(np.full(k.size, r, np.int32))
             khz.append(k)
         return np.concatenate(src), np.concatenate(khz)
+
+
+# ------------------------------------------------------------------ wideband splitter (include/sdr_amd.h, sdr_split_*)
+def split_geometry(mode: int, W: int) -> tuple[int, int, int, int, int]:
+    """(rows R = 2 W - 1, taps T = 16 W, wide_iq = W * block_iq, half_khz = N / 2, default shift) of a
+    mode and a width factor W in {4, 8, 10} (host only)."""
+    v = [C.c_int(0) for _ in range(5)]
+    check(lib().sdr_split_geometry(mode, W, *[C.byref(x) for x in v]), "sdr_split_geometry")
+    return tuple(x.value for x in v)
+
+
+def split_taps(W: int):
+    """The splitter's tap table: int16 [R][T][2] (g_re, g_im) (host only)."""
+    import numpy as np
+    n = C.c_int(0)
+    check(lib().sdr_split_taps(W, None, 0, C.byref(n)), "sdr_split_taps")
+    g = np.zeros((2 * W - 1, 16 * W, 2), np.int16)
+    check(lib().sdr_split_taps(W, g.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "sdr_split_taps")
+    return g
+
+
+class Splitter:
+    """`nwide` wide int8 I/Q captures at W * rf_Fs into nwide * (2 W - 1) capture rows at rf_Fs, the rows
+    sdr_frontend_tuned and the Scanner read (sdr_split_*). Its own handle: no channels, any stream."""
+
+    def __init__(self, W: int, nwide: int, mode: int = 0, device: int = 0, shift=None):
+        h = C.c_void_p()
+        check(lib().sdr_split_create(C.byref(h), device, mode, W, nwide, 0 if shift is None else int(shift)),
+              "sdr_split_create")
+        self._h = h
+        self.W, self.nwide, self.mode, self.device = W, nwide, mode, device
+        self.rows, self.taps, self.wide_iq, self.half_khz, d = split_geometry(mode, W)
+        self.shift = d if shift is None or shift <= 0 else int(shift)
+        self.block_iq = self.wide_iq // W
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sdr_split_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().sdr_split_reset(self._h, _stream(stream)), "sdr_split_reset")
+
+    def block(self, wide, out=None, stream=None):
+        """wide: int8 [nwide][2*W*block_iq] (device). Returns the uint8 rows [nwide*R][2*block_iq] (out, or
+        a new tensor); enqueues, no sync."""
+        import torch
+        if wide.dim() != 2 or wide.shape[0] != self.nwide or wide.dtype != torch.int8:
+            raise SdrError(f"Splitter.block: expected int8 [{self.nwide}][2*W*block_iq] streams", -1)
+        if out is None:
+            out = torch.empty((self.nwide * self.rows, 2 * self.block_iq), dtype=torch.uint8, device=wide.device)
+        elif out.dim() != 2 or out.shape[0] != self.nwide * self.rows or out.dtype != torch.uint8:
+            raise SdrError(f"Splitter.block: expected uint8 [{self.nwide * self.rows}][2*block_iq] rows", -1)
+        ws = _row_stride(wide) if wide.shape[0] > 1 else int(wide.shape[1])
+        check(lib().sdr_split_block(self._h, _ptr(wide), ws, _ptr(out), _row_stride(out), _stream(stream)),
+              "sdr_split_block")
+        return out
+
+    def clips(self, stream=None):
+        """numpy int64 [nwide][R]: clipped output components since the last reset; synchronises the stream."""
+        import numpy as np
+        c = np.zeros((self.nwide, self.rows), np.int64)
+        check(lib().sdr_split_clips(self._h, c.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_split_clips")
+        return c
 
 
 # ------------------------------------------------------------------ reception meter (include/sdr_amd.h, sdr_meter_*)

@@ -5,6 +5,7 @@
 //   sdr_kernels.hip    IF FIRs, resamplers, mixers, RDS bits, context and the C ABI
 //   sdr_scan.hip       band scan of the capture rows
 //   sdr_meter.hip      reception meter: per-channel readings of a block's rows
+//   sdr_split.hip      wideband splitter: a wide s8 capture into the capture rows (its own handle)
 //
 // Layout: channel-major [nch][len]. Every f32 stream that a later FIR/resampler reads with
 // look-back is kept "extended": [2 parities][nch][HIST + len], the first HIST samples being the

@@ -4,6 +4,8 @@
 //   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
 //             [--deemph US] [--blend]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
+//   sdr_multi NCH --wide W [--shift S] --tune FILE ...          (the receiver on wide captures)
+//   sdr_multi NWIDE --wide W [--shift S] --scan ...             (the scan of wide captures)
 //
 // Input: u8 I/Q, block after block, each block NCH rows of 2*block_iq bytes (channel after
 // channel: the [block][channel][bytes] layout of bench.py). Output: PREFIX.pcm -- per block NCH
@@ -24,6 +26,13 @@
 // --meter): the audio finishing stage (include/sdr_multi_audio.h) -- PREFIX.audio, in the layout of PREFIX.pcm,
 // holds the audio de-emphasised with US microseconds (75 when only --blend is given) and, with --blend,
 // blended to mono where the meter finds no pilot; every other file is that of a run without them.
+// --wide W (4, 8 or 10; --shift S: the splitter's output shift, default 14, 15, 16): the input is wide
+// signed 8-bit I/Q at W * rf_Fs (include/sdr_multi_wide.h, include/sdr_wide_scan.h) -- per block, rows of
+// 2*W*block_iq int8 bytes, each cut by the wideband splitter into 2W-1 capture rows; capture row w*(2W-1)+r
+// is row r of wide stream w. With --tune the input holds ceil((max(src) + 1) / (2W-1)) wide streams per
+// block; with --scan NWIDE wide streams are scanned and PREFIX.stations names the capture rows, so
+// `sdr_multi <n> --wide W --tune PREFIX.stations` receives what `sdr_multi NWIDE --wide W --scan` found.
+// The summary line counts the wide bytes read; clip counts go to stderr when any are non-zero.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -35,7 +44,9 @@
 #include "sdr_multi_audio.h"
 #include "sdr_multi_meter.h"
 #include "sdr_multi_tuned.h"
+#include "sdr_multi_wide.h"
 #include "sdr_scan_run.h"
+#include "sdr_wide_scan.h"
 
 namespace {
 [[noreturn]] void usage() {
@@ -43,11 +54,14 @@ namespace {
                          "[--tune FILE] [--meter] [--deemph US] [--blend]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
+                         "       sdr_multi NCH --wide W [--shift S] --tune FILE ...   |   sdr_multi NWIDE --wide W [--shift S] --scan ...\n"
                          "  --tune FILE: NCH lines \"src khz\"; the input holds max(src)+1 capture rows per block\n"
                          "  --meter: also write PREFIX.meter (64-byte readings per channel and block) and PREFIX.status\n"
                          "  --deemph US: also write PREFIX.audio, the PCM de-emphasised with 0, 50 or 75 microseconds\n"
                          "  --blend: PREFIX.audio blended to mono where the meter finds no pilot (needs --meter)\n"
-                         "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n");
+                         "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n"
+                         "  --wide W: the input is wide int8 I/Q at W (4, 8, 10) times rf_Fs, rows of 2*W*block_iq bytes, each\n"
+                         "            split into 2W-1 capture rows (--shift S: output shift 1-24); needs --tune or --scan\n");
     std::exit(1);
 }
 }  // namespace
@@ -60,6 +74,7 @@ int main(int argc, char** argv) {
     std::string in = "-", out = "sdr_multi", tune_path;
     if (o.nch <= 0) usage();
     bool scan = false, meter = false, blend = false, finish = false;
+    int wide_w = 0, wide_shift = 0;
     sdr_audio_opts ao{};
     sdr_audio_opts_default(&ao);
     sdr_scan_run_opts so{};
@@ -72,6 +87,14 @@ int main(int argc, char** argv) {
         else if (a == "--cus" && i + 1 < argc) o.pll_cus = std::atoi(argv[++i]);
         else if (a == "--tune" && i + 1 < argc) tune_path = argv[++i];
         else if (a == "--scan") scan = true;
+        else if (a == "--wide" && i + 1 < argc) {
+            wide_w = std::atoi(argv[++i]);
+            if (wide_w != 4 && wide_w != 8 && wide_w != 10) usage();
+        }
+        else if (a == "--shift" && i + 1 < argc) {
+            wide_shift = std::atoi(argv[++i]);
+            if (wide_shift < 1 || wide_shift > 24) usage();
+        }
         else if (a == "--meter") meter = true;
         else if (a == "--blend") blend = finish = true;
         else if (a == "--deemph" && i + 1 < argc) {
@@ -90,6 +113,32 @@ int main(int argc, char** argv) {
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();
     if (blend && !meter) usage();
+    if (wide_shift && !wide_w) usage();
+    if (wide_w && !scan && tune_path.empty()) usage();        // a wide run is always tuned
+    if (scan && wide_w) {
+        if (!tune_path.empty() || meter || finish) usage();
+        const std::string list = out + ".stations";
+        sdr_wide_scan_opts wo{};
+        wo.nwide = o.nch;
+        wo.W = wide_w;
+        wo.shift = wide_shift;
+        wo.mode = o.mode;
+        wo.device = o.device;
+        wo.in_path = o.in_path;
+        wo.out_path = list.c_str();
+        wo.max_blocks = so.max_blocks;
+        wo.pick = so.pick;
+        sdr_wide_scan_stats ws{};
+        const int rc = sdr_wide_scan_run(&wo, &ws);
+        if (rc != SDR_OK) {
+            std::fprintf(stderr, "sdr_multi: %d %s\n", rc, ws.error);
+            return 1;
+        }
+        std::fprintf(stderr, "sdr_multi: scan: %d stations in %d wide streams x %d rows (%lld segments per row)\n", ws.stations,
+                     wo.nwide, 2 * wide_w - 1, ws.segments);
+        if (ws.clips) std::fprintf(stderr, "sdr_multi: splitter: %lld output components clipped\n", ws.clips);
+        return 0;
+    }
     if (scan) {
         if (!tune_path.empty() || meter || finish) usage();   // a scan writes a tuning, it does not take one (nor does it demodulate)
         const std::string list = out + ".stations";
@@ -132,11 +181,22 @@ int main(int argc, char** argv) {
         tune.src = src.data();
         tune.khz = khz.data();
     }
-    const int rows = tune_path.empty() ? o.nch : tune.nsrc;
+    const int wide_r = 2 * wide_w - 1;
+    sdr_multi_wide wd{};
+    std::vector<long long> clips;
+    if (wide_w) {
+        wd.W = wide_w;
+        wd.nwide = (tune.nsrc + wide_r - 1) / wide_r;
+        wd.shift = wide_shift;
+        clips.assign((size_t)(wd.nwide > 0 ? wd.nwide : 1) * wide_r, 0);
+        wd.clips = clips.data();
+    }
+    const int rows = wide_w ? wd.nwide : tune_path.empty() ? o.nch : tune.nsrc;
     sdr_meter_opts mo{};
     sdr_meter_opts_default(&mo);
     const sdr_multi_tuning* tp = tune_path.empty() ? nullptr : &tune;
-    const int rc = finish  ? sdr_multi_run_finished(&o, tp, meter ? &mo : nullptr, &ao, blend ? 1 : 0, &st)
+    const int rc = wide_w  ? sdr_multi_run_wide(&o, &wd, tp, meter ? &mo : nullptr, finish ? &ao : nullptr, blend ? 1 : 0, &st)
+                   : finish ? sdr_multi_run_finished(&o, tp, meter ? &mo : nullptr, &ao, blend ? 1 : 0, &st)
                    : meter ? sdr_multi_run_metered(&o, tp, &mo, &st)
                            : sdr_multi_run_tuned(&o, tp, &st);
     if (rc != SDR_OK) {
@@ -144,20 +204,25 @@ int main(int argc, char** argv) {
                      tune_path.empty() ? "" : " (--tune: 0 <= src < NCH rows, -N/2 < khz <= N/2, N = rf_Fs / 1000)");
         return 1;
     }
+    for (size_t i = 0; i < clips.size(); i++)
+        if (clips[i])
+            std::fprintf(stderr, "sdr_multi: splitter: wide stream %zu row %zu: %lld output components clipped\n",
+                         i / (size_t)wide_r, i % (size_t)wide_r, clips[i]);
     sdr_ctx* probe = nullptr;   // sizes of the mode
     sdr_info info{};
     if (sdr_ctx_create(&probe, o.device, 1, o.mode, 0, 0) != SDR_OK || sdr_ctx_info(probe, &info) != SDR_OK) return 1;
     sdr_ctx_destroy(probe);
     const double samples = (double)st.blocks * o.nch * info.block_iq;
     const double signal_s = (double)st.blocks * info.block_iq / (double)info.rf_Fs;
-    const double in_gb = (double)st.blocks * rows * 2.0 * info.block_iq / 1e9;
+    const double in_gb = (double)st.blocks * rows * 2.0 * info.block_iq * (wide_w ? wide_w : 1) / 1e9;   // (a wide run: the wide bytes)
     char after0[128] = "after block 0 n/a (fewer than 2 blocks)";
     if (st.blocks >= 2 && st.steady_seconds > 0)
         std::snprintf(after0, sizeof(after0), "after block 0 %.1f MS/s (%.1fx real time)",
                       (double)(st.blocks - 1) * o.nch * info.block_iq / st.steady_seconds / 1e6,
                       (double)(st.blocks - 1) * info.block_iq / (double)info.rf_Fs / st.steady_seconds);
     char rows_txt[64] = "";   // a tuned run reads fewer rows than it has channels
-    if (!tune_path.empty()) std::snprintf(rows_txt, sizeof(rows_txt), " (from %d capture rows per block)", rows);
+    if (wide_w) std::snprintf(rows_txt, sizeof(rows_txt), " (from %d wide streams x %d rows per block)", rows, wide_r);
+    else if (!tune_path.empty()) std::snprintf(rows_txt, sizeof(rows_txt), " (from %d capture rows per block)", rows);
     std::fprintf(stderr,
                  "sdr_multi: %d channels%s x %lld blocks in %.3f s: %.1f MS/s I/Q, %.1fx real time; %s; PLLs %s "
                  "(%.4f ms per block); input read %.3f s (%.1f GB/s), H2D %.3f s GPU time (%.1f GB/s), "

@@ -8,7 +8,9 @@
 // another's GPU work except through the queue's prepare() ordering):
 //   reader  file/stdin -> pinned ring slot (byte-stream input only)
 //   RF      [slot -H2D (copy stream)-> d_iq] or the device-resident block; sdr_frontend (a tuned run,
-//           include/sdr_multi_tuned.h: sdr_frontend_tuned on nsrc capture rows per block); fm_demod ->
+//           include/sdr_multi_tuned.h: sdr_frontend_tuned on nsrc capture rows per block; a wide run,
+//           include/sdr_multi_wide.h: sdr_split_block of the wide block into one of two row buffers
+//           first, on the same stream, and sdr_frontend_tuned on that buffer); fm_demod ->
 //           a recycled FmBatch (device), event, push                     rffrontend.cpp:45-76
 //   audio   wait_and_pop(0); sdr_push_fm_demod; stereo_pre; PLL; stereo_post; L/R -D2H-> pinned;
 //           the write of block b-1 overlaps the GPU work of block b          stereo.cpp:69-114
@@ -57,6 +59,7 @@
 #include "sdr_multi_audio.h"
 #include "sdr_multi_meter.h"
 #include "sdr_multi_tuned.h"
+#include "sdr_multi_wide.h"
 
 using sdrhost::check_hip;
 using sdrhost::check_sdr;
@@ -368,8 +371,11 @@ struct Shared {
     sdr_multi_opts o{};
     MeterOut* meter = nullptr;           // a metered run (sdr_multi_run_metered)
     AudioFin* fin = nullptr;             // a finished run (sdr_multi_run_finished)
-    int rows = 0;                        // input rows per block: nch, or a tuned run's nsrc
+    int rows = 0;                        // input rows per block: nch, a tuned run's nsrc, a wide run's nwide
     bool tuned = false;
+    sdr_split* split = nullptr;          // a wide run (sdr_multi_run_wide): the input rows are wide int8 streams
+    size_t in_row = 0;                   // bytes of an input row: 2*block_iq, or a wide run's 2*W*block_iq
+    int split_rows = 0;                  // a wide run's capture rows per block, nwide * (2 W - 1)
     AudioRes ar;
     RdsRes rr;
     hipStream_t s_d2h = nullptr;         // the L/R copies when not on s_post (SDR_MULTI_D2H=copy)
@@ -457,7 +463,7 @@ void rf_thread(Shared* sh) {
     sh->arrive_and_wait();
     sdr_ctx* ctx = sh->ctx[0];
     const sdr_info& in = sh->info;
-    const size_t row = 2 * (size_t)in.block_iq, bytes = row * (size_t)sh->rows;
+    const size_t row = 2 * (size_t)in.block_iq, bytes = sh->in_row * (size_t)sh->rows;
     hipStream_t s = sh->s_fe;
     const bool dev_in = o.in_path == nullptr;
     uint8_t* d_iq[2] = {};
@@ -474,6 +480,16 @@ void rf_thread(Shared* sh) {
             sh->h2d_ms += elapsed_ms(c0[t], c1[t]);
         }
     };
+    // a wide run: two buffers of capture rows. Block b's splitter writes buffer b & 1 on the block's
+    // front-end stream, in front of the front end that reads it; block b + 2 may be on another stream
+    // than block b (the first block's all-CU stream), so its splitter waits for rows_done of block b.
+    uint8_t* d_rows[2] = {};
+    hipEvent_t rows_done[2] = {};
+    if (sh->split)
+        for (int k = 0; k < 2; k++) {
+            check_hip(hipMalloc(reinterpret_cast<void**>(&d_rows[k]), row * (size_t)sh->split_rows), "hipMalloc");
+            rows_done[k] = new_event();
+        }
     Reader* rd = nullptr;
     if (!dev_in) {
         for (int k = 0; k < 2; k++) {
@@ -486,7 +502,7 @@ void rf_thread(Shared* sh) {
     }
     for (long long b = 0;; b++) {
         const uint8_t* src = nullptr;
-        size_t stride = row;
+        size_t stride = sh->in_row;
         if (dev_in) {
             if (b >= o.nblocks) break;
             src = o.d_iq + (size_t)b * o.block_stride;
@@ -514,7 +530,14 @@ void rf_thread(Shared* sh) {
         if (b == 1) sh->t_block1 = std::chrono::steady_clock::now();
         const hipStream_t sf = fe_stream(sh, b);
         if (!dev_in && sf != s) check_hip(hipStreamWaitEvent(sf, h2d[(int)(b & 1)], 0), "hipStreamWaitEvent");
-        if (sh->tuned) check_sdr(sdr_frontend_tuned(ctx, src, stride, sf), "sdr_frontend_tuned");
+        if (sh->split) {
+            const int k = (int)(b & 1);
+            if (b >= 2) check_hip(hipStreamWaitEvent(sf, rows_done[k], 0), "hipStreamWaitEvent");
+            check_sdr(sdr_split_block(sh->split, reinterpret_cast<const int8_t*>(src), stride, d_rows[k], row, sf),
+                      "sdr_split_block");
+            check_sdr(sdr_frontend_tuned(ctx, d_rows[k], row, sf), "sdr_frontend_tuned");
+            check_hip(hipEventRecord(rows_done[k], sf), "hipEventRecord");
+        } else if (sh->tuned) check_sdr(sdr_frontend_tuned(ctx, src, stride, sf), "sdr_frontend_tuned");
         else check_sdr(sdr_frontend(ctx, src, stride, sf), "sdr_frontend");
         if (!dev_in) check_hip(hipEventRecord(fe_done[(int)(b & 1)], sf), "hipEventRecord");
         FmBatch* fb = sh->q.acquire();
@@ -528,6 +551,10 @@ void rf_thread(Shared* sh) {
     }
     sh->q.push(nullptr);                                    // end of stream
     check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
+    for (int k = 0; k < 2 && sh->split; k++) {
+        (void)hipFree(d_rows[k]);
+        (void)hipEventDestroy(rows_done[k]);
+    }
     if (!dev_in) {
         harvest(sh->blocks, true);
         sh->read_s = rd->read_s;
@@ -850,14 +877,24 @@ bool tuning_valid(const sdr_multi_opts* o, const sdr_multi_tuning* t) {
 }
 
 int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo, const sdr_audio_opts* ao,
-              bool blend, sdr_multi_stats* stats) {
+              bool blend, sdr_multi_stats* stats, const sdr_multi_wide* wide = nullptr) {
     if (!opts || opts->nch <= 0 || (!opts->in_path && (!opts->d_iq || opts->nblocks <= 0)))
         return SDR_E_INVALID;
     if (tune && !tuning_valid(opts, tune)) return SDR_E_INVALID;
+    int wide_R = 0, wide_iq = 0;
+    if (wide) {   // a wide run is always tuned, on rows the splitter makes
+        if (!tune || wide->nwide < 1 || wide->nwide > 4096 || wide->shift > 24 ||
+            sdr_split_geometry(opts->mode, wide->W, &wide_R, nullptr, &wide_iq, nullptr, nullptr) != SDR_OK ||
+            tune->nsrc > wide->nwide * wide_R)
+            return SDR_E_INVALID;
+        if (!opts->in_path && ((opts->row_stride & 3) || (reinterpret_cast<uintptr_t>(opts->d_iq) & 3) ||
+                               (opts->block_stride & 3) || opts->row_stride < 2 * (size_t)wide_iq))
+            return SDR_E_INVALID;
+    }
     Shared sh;
     sh.o = *opts;
     sh.tuned = tune != nullptr;
-    sh.rows = tune ? tune->nsrc : opts->nch;
+    sh.rows = wide ? wide->nwide : tune ? tune->nsrc : opts->nch;
     const sdr_multi_opts& o = sh.o;
     check_hip(hipSetDevice(o.device), "hipSetDevice");
     // SDR_MULTI_TRACE=1: the set-up and tear-down phases' host times on stderr
@@ -879,11 +916,16 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
                   "sdr_tuner_set");
     check_sdr(sdr_ctx_info(sh.ctx[0], &sh.info), "sdr_ctx_info");
     const size_t row = 2 * (size_t)sh.info.block_iq;
-    if (!o.in_path && o.row_stride < row) {
+    sh.in_row = wide ? 2 * (size_t)wide_iq : row;
+    if (!o.in_path && o.row_stride < sh.in_row) {
         for (sdr_ctx* c : sh.ctx) ctx_put(c);
         return SDR_E_INVALID;
     }
-    sh.nblocks_known = o.in_path ? regular_file_blocks(o.in_path, row * (size_t)sh.rows) : o.nblocks;
+    if (wide) {
+        sh.split_rows = wide->nwide * wide_R;
+        check_sdr(sdr_split_create(&sh.split, o.device, o.mode, wide->W, wide->nwide, wide->shift), "sdr_split_create");
+    }
+    sh.nblocks_known = o.in_path ? regular_file_blocks(o.in_path, sh.in_row * (size_t)sh.rows) : o.nblocks;
     // streams: the PLLs on [0, pll_cus) (halves), everything else on the rest
     const int half = o.pll_cus / 2;
     if (half > 0) {
@@ -1016,6 +1058,10 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
         }
     }
     check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    if (sh.split) {
+        if (wide->clips) check_sdr(sdr_split_clips(sh.split, wide->clips, nullptr), "sdr_split_clips");
+        check_sdr(sdr_split_destroy(sh.split), "sdr_split_destroy");
+    }
     for (auto& fb : batches) {
         (void)hipFree(fb.d_fm);
         (void)hipEventDestroy(fb.ready);
@@ -1074,4 +1120,15 @@ extern "C" int sdr_multi_run_finished(const sdr_multi_opts* opts, const sdr_mult
     float a = 0.0f, b = 0.0f;   // what sdr_audio_create would refuse, before anything starts
     if (sdr_audio_coeffs(opts->mode, ao->tau_us, &a, &b) != SDR_OK || !(ao->blend_hi > ao->blend_lo)) return SDR_E_INVALID;
     return multi_run(opts, tune, mo, ao, blend != 0, stats);
+}
+
+extern "C" int sdr_multi_run_wide(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
+                                  const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, sdr_multi_stats* stats) {
+    if (!wide) return sdr_multi_run_finished(opts, tune, mo, ao, blend, stats);
+    if (!opts || !tune || (blend && (!mo || !ao))) return SDR_E_INVALID;
+    if (ao) {   // what sdr_audio_create would refuse, before anything starts (as sdr_multi_run_finished)
+        float a = 0.0f, b = 0.0f;
+        if (sdr_audio_coeffs(opts->mode, ao->tau_us, &a, &b) != SDR_OK || !(ao->blend_hi > ao->blend_lo)) return SDR_E_INVALID;
+    }
+    return multi_run(opts, tune, mo, ao, blend != 0, stats, wide);
 }

@@ -9,7 +9,7 @@ d=build/variants/$name.obj
 mkdir -p $d
 common="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-gpu-flush-denormals-to-zero -mllvm -pragma-unroll-threshold=1000000 -Iinclude"
 pids=""
-for f in sdr_kernels.hip sdr_frontend.hip sdr_pll.hip sdr_scan.hip sdr_meter.hip sdr_audio.hip sdr_taps.cpp; do
+for f in sdr_kernels.hip sdr_frontend.hip sdr_pll.hip sdr_scan.hip sdr_meter.hip sdr_audio.hip sdr_split.hip sdr_taps.cpp; do
   extra=""
   case $f in
     sdr_kernels.hip) extra="-fno-slp-vectorize ${KFLAGS:-}";;
