@@ -23,8 +23,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -pthread -D__HIP_PLATFORM_AMD__ 
              -Iinclude -Iinclude/dropin -I$(PKG)/host
 HOSTLIB   := $(PKG)/libsdr_host.so
 HOSTSRCS  := $(PKG)/host/dropin_primitives.cpp $(PKG)/host/dropin_stages.cpp $(PKG)/host/rds_frame.cpp \
-             $(PKG)/host/sdr_multi_engine.cpp $(PKG)/host/sdr_scan_run.cpp \
-             $(PKG)/host/sdr_wide_scan.cpp
+             $(PKG)/host/sdr_multi_engine.cpp $(PKG)/host/sdr_scan_run.cpp
 HOSTHDRS  := $(wildcard include/dropin/*.h) $(PKG)/host/hip_util.h include/sdr_amd.h include/sdr_multi.h \
              include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h \
              include/sdr_multi_wide.h include/sdr_wide_scan.h

@@ -1,6 +1,6 @@
 /* sdr_wide_scan.h -- the band scan over a wide capture file: the file loop behind
  * `sdr_multi NWIDE --wide W --scan`, exported from libsdr_host.so
- * (real-time-sdr_amd/host/sdr_wide_scan.cpp) on the splitter and the scanner of include/sdr_amd.h
+ * (real-time-sdr_amd/host/sdr_scan_run.cpp) on the splitter and the scanner of include/sdr_amd.h
  * (sdr_split_*, sdr_scan_*).
  *
  * The input is the byte stream sdr_multi --wide reads (include/sdr_multi_wide.h): int8 I/Q, block after

@@ -31,9 +31,24 @@
 // run on the CUs the PLLs leave. A consumer's wait on s_post is enqueued after its signal on s_fe
 // and its next parity reuse on s_fe after its post on s_post, so no wait on one stream can sit in
 // front of the work it waits for on the other.
+//
+// A run is described once (RunSpec), judged once, before any device call (validate), and owns what it
+// makes: every event, buffer, stream, context and file is released by the destructor of the object
+// that holds it, in the reverse order of declaration.
+//
+// Environment switches, read once at the start of a run (Switches):
+//   SDR_MULTI_READERS=n       pread threads per block of a regular input file (default 8; 1: fread)
+//   SDR_MULTI_POSTS=2         the RDS consumer's post part on a stream of its own
+//   SDR_MULTI_EDGES=0         no all-CU stream for the first block's front-end side and the last's post side
+//   SDR_MULTI_FILL=0          block 1's front end does not wait for the consumers' block 0 pre parts
+//   SDR_MULTI_TRACE=1         the set-up and tear-down phases' host times on stderr
+//   SDR_MULTI_CTX_CACHE=0     contexts made and destroyed per run instead of pooled
+//   SDR_MULTI_STREAM_CACHE=0  CU-masked streams likewise
+//   SDR_MULTI_PIN_CACHE=0     pinned output buffers likewise
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <cstdint>
@@ -43,6 +58,7 @@
 #include <deque>
 #include <iostream>
 #include <mutex>
+#include <optional>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -63,105 +79,180 @@
 
 using sdrhost::check_hip;
 using sdrhost::check_sdr;
+using sdrhost::DevBuf;
 using sdrhost::die;
 
 namespace {
 
-hipStream_t plain_stream() {
-    hipStream_t h = nullptr;
-    check_hip(hipStreamCreateWithFlags(&h, hipStreamNonBlocking), "hipStreamCreate");
-    return h;
-}
-
-// a stream on CUs [first, first + n) (exclude = 0) or on every other CU (exclude = 1); its own
-// hardware queue (sdr_stream_create_cu_range). Streams outlive a run, like the pinned buffers below:
-// making and destroying the six masked streams took ~30 + ~40 ms per run, in which the GPU idled
-// and its clock fell before the next run's first blocks (profiles/r06/queue_fill/). A run takes idle
-// pooled streams of its CU range; SDR_MULTI_STREAM_CACHE=0: made and destroyed per run.
-struct PooledStream {
-    int device, first, n, exclude;
-    void* s;
+// ------------------------------------------------------------------ what a run is
+struct RunSpec {
+    const sdr_multi_opts* o = nullptr;
+    const sdr_multi_tuning* tune = nullptr;   // shared captures (sdr_multi_run_tuned)
+    const sdr_meter_opts* meter = nullptr;    // the reception meter (sdr_multi_run_metered)
+    const sdr_audio_opts* audio = nullptr;    // audio finishing (sdr_multi_run_finished)
+    bool blend = false;                       //   its blend targets follow the meter's rows
+    const sdr_multi_wide* wide = nullptr;     // wide captures (sdr_multi_run_wide)
 };
-std::mutex g_stream_mu;
-std::vector<PooledStream> g_stream_free, g_stream_live;
-bool stream_cache_on() {
-    const char* e = std::getenv("SDR_MULTI_STREAM_CACHE");
-    return !e || std::atoi(e) != 0;
-}
-hipStream_t masked_stream(int device, int first, int n, int exclude) {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    for (size_t i = 0; i < g_stream_free.size(); i++) {
-        const PooledStream& p = g_stream_free[i];
-        if (p.device == device && p.first == first && p.n == n && p.exclude == exclude) {
-            g_stream_live.push_back(p);
-            g_stream_free.erase(g_stream_free.begin() + (long)i);
-            return (hipStream_t)g_stream_live.back().s;
-        }
+
+// Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused.
+bool validate(const RunSpec& r) {
+    const sdr_multi_opts* o = r.o;
+    if (!o || (r.blend && (!r.meter || !r.audio))) return false;
+    if (r.audio) {   // what sdr_audio_create would refuse
+        float a = 0.0f, b = 0.0f;
+        if (sdr_audio_coeffs(o->mode, r.audio->tau_us, &a, &b) != SDR_OK || !(r.audio->blend_hi > r.audio->blend_lo)) return false;
     }
-    void* s = nullptr;
-    check_sdr(sdr_stream_create_cu_range(&s, device, first, n, exclude), "sdr_stream_create_cu_range");
-    g_stream_live.push_back({device, first, n, exclude, s});
-    return (hipStream_t)s;
-}
-// the end of a run: the stream (idle by then) back to the pool, or destroyed
-void release_masked(hipStream_t h) {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    for (size_t i = 0; i < g_stream_live.size(); i++)
-        if (g_stream_live[i].s == (void*)h) {
-            if (stream_cache_on()) g_stream_free.push_back(g_stream_live[i]);
-            else (void)sdr_stream_destroy(h);
-            g_stream_live.erase(g_stream_live.begin() + (long)i);
-            return;
-        }
+    if (o->nch <= 0 || (!o->in_path && (!o->d_iq || o->nblocks <= 0))) return false;
+    if (const sdr_multi_tuning* t = r.tune) {   // the tuning's bounds (sdr_tuner_set's)
+        int N = 0;
+        if (sdr_tuner_table(o->mode, nullptr, 0, &N) != SDR_OK) return false;
+        if (t->nsrc < 1 || t->nsrc > o->nch || !t->src || !t->khz) return false;
+        for (int c = 0; c < o->nch; c++)
+            if (t->src[c] < 0 || t->src[c] >= t->nsrc || 2 * (long long)t->khz[c] <= -(long long)N || 2 * (long long)t->khz[c] > N)
+                return false;
+    }
+    int in_iq = 0;   // samples of an input row; left 0 for a mode the scanner does not know: sdr_ctx_create ends that run
+    if (const sdr_multi_wide* w = r.wide) {   // a wide run is always tuned, on rows the splitter makes
+        int R = 0;
+        if (!r.tune || w->nwide < 1 || w->nwide > 4096 || w->shift > 24 ||
+            sdr_split_geometry(o->mode, w->W, &R, nullptr, &in_iq, nullptr, nullptr) != SDR_OK || r.tune->nsrc > w->nwide * R)
+            return false;
+        if (!o->in_path && ((o->row_stride & 3) || (reinterpret_cast<uintptr_t>(o->d_iq) & 3) || (o->block_stride & 3))) return false;
+    } else {
+        (void)sdr_scan_geometry(o->mode, nullptr, nullptr, &in_iq);   // block_iq, the contexts' (sdr_ctx_info)
+    }
+    return o->in_path || o->row_stride >= 2 * (size_t)in_iq;
 }
 
-// contexts outlive a run too (SDR_MULTI_CTX_CACHE=0: made and destroyed per run): a later run with
-// the same channels, mode and flags takes an idle one back to the reference's initial state
-// (sdr_ctx_reset) in ~1 ms instead of ~3 ms to make and ~10 ms to destroy, with the GPU idle meanwhile
-struct PooledCtx {
-    int device, nch, mode, rds_on, flags;
-    sdr_ctx* c;
+struct Switches {   // the file's header comment says what each does
+    static int num(const char* name, int unset) {
+        const char* e = std::getenv(name);
+        return e ? std::atoi(e) : unset;
+    }
+    int readers = std::max(1, num("SDR_MULTI_READERS", 8));
+    bool posts2 = num("SDR_MULTI_POSTS", 1) == 2, edges = num("SDR_MULTI_EDGES", 1) != 0;
+    bool fill = num("SDR_MULTI_FILL", 1) != 0, trace = num("SDR_MULTI_TRACE", 0) != 0;
+    bool ctx_cache = num("SDR_MULTI_CTX_CACHE", 1) != 0, stream_cache = num("SDR_MULTI_STREAM_CACHE", 1) != 0;
+    bool pin_cache = num("SDR_MULTI_PIN_CACHE", 1) != 0;
 };
-std::mutex g_ctx_mu;
-std::vector<PooledCtx> g_ctx_free;
-std::vector<PooledCtx> g_ctx_live;
-bool ctx_cache_on() {
-    const char* e = std::getenv("SDR_MULTI_CTX_CACHE");
-    return !e || std::atoi(e) != 0;
-}
-sdr_ctx* ctx_get(int device, int nch, int mode, int rds_on, int flags) {
-    std::lock_guard<std::mutex> lk(g_ctx_mu);
-    for (size_t i = 0; i < g_ctx_free.size(); i++) {
-        const PooledCtx& p = g_ctx_free[i];
-        if (p.device == device && p.nch == nch && p.mode == mode && p.rds_on == rds_on && p.flags == flags) {
-            check_sdr(sdr_ctx_reset(p.c, nullptr), "sdr_ctx_reset");
-            g_ctx_live.push_back(p);
-            g_ctx_free.erase(g_ctx_free.begin() + (long)i);
-            return g_ctx_live.back().c;
-        }
-    }
-    sdr_ctx* c = nullptr;
-    check_sdr(sdr_ctx_create(&c, device, nch, mode, rds_on, flags), "sdr_ctx_create");
-    g_ctx_live.push_back({device, nch, mode, rds_on, flags, c});
-    return c;
-}
-void ctx_put(sdr_ctx* c) {   // after the run's streams have drained
-    std::lock_guard<std::mutex> lk(g_ctx_mu);
-    for (size_t i = 0; i < g_ctx_live.size(); i++)
-        if (g_ctx_live[i].c == c) {
-            if (ctx_cache_on()) g_ctx_free.push_back(g_ctx_live[i]);
-            else sdr_ctx_destroy(c);
-            g_ctx_live.erase(g_ctx_live.begin() + (long)i);
-            return;
-        }
-    sdr_ctx_destroy(c);
-}
 
-hipEvent_t new_event() {
+// ------------------------------------------------------------------ owners: released where they go out of scope
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    void operator=(const NoCopy&) = delete;
+};
+
+struct Event : NoCopy {
     hipEvent_t e = nullptr;
-    check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-    return e;
-}
+    void make(unsigned flags = hipEventDisableTiming) { check_hip(hipEventCreateWithFlags(&e, flags), "hipEventCreate"); }
+    void make_timing() { make(hipEventDefault); }
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+struct File : NoCopy {   // an output file of the run
+    FILE* f = nullptr;
+    void open(const std::string& path, const char* mode) {
+        f = std::fopen(path.c_str(), mode);
+        if (!f) die("cannot write " + path);
+    }
+    ~File() {
+        if (f) std::fclose(f);
+    }
+    operator FILE*() const { return f; }
+};
+
+// Idle objects kept for the process's later runs, by key. Contexts, CU-masked streams and pinned
+// buffers outlive a run: making and destroying them took ~13 ms (contexts: ~3 ms to make and ~10 ms to
+// destroy, against ~1 ms for sdr_ctx_reset), ~70 ms (the six masked streams) and ~50 ms (pinning ~25 MB)
+// per run, in which the GPU idled and its clock fell before the next run's first blocks
+// (profiles/r06/queue_fill/). A handle below takes an idle object of its key or makes one, and at its end
+// gives it back -- or, with its cache switched off, destroys it. Pooled objects live until the process exits.
+template <typename Key, typename T>
+struct Pool {
+    std::mutex mu;
+    std::vector<std::pair<Key, T>> idle;
+    bool take(const Key& key, T* out) {
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = idle.size(); i-- > 0;)   // the last given first: a run releases in the reverse order of
+            if (idle[i].first == key) {          // taking, so the next run has each object in the role it had
+                *out = idle[i].second;
+                idle.erase(idle.begin() + (long)i);
+                return true;
+            }
+        return false;
+    }
+    void give(const Key& key, T v) {
+        std::lock_guard<std::mutex> lk(mu);
+        idle.emplace_back(key, v);
+    }
+};
+Pool<std::array<int, 4>, hipStream_t> g_streams;   // device, first CU, CUs, exclude
+Pool<std::array<int, 5>, sdr_ctx*> g_ctxs;         // device, nch, mode, rds_on, flags
+Pool<size_t, void*> g_pinned;                      // bytes
+
+struct Stream : NoCopy {
+    hipStream_t s = nullptr;
+    std::array<int, 4> key{};
+    bool masked = false, keep = false;
+    void plain() { check_hip(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate"); }
+    // on CUs [first, first + n) (exclude = 0) or on every other CU (exclude = 1); its own hardware queue
+    void on_cus(int device, int first, int n, int exclude, bool cache) {
+        key = {device, first, n, exclude};
+        masked = true;
+        keep = cache;
+        if (g_streams.take(key, &s)) return;
+        void* h = nullptr;
+        check_sdr(sdr_stream_create_cu_range(&h, device, first, n, exclude), "sdr_stream_create_cu_range");
+        s = (hipStream_t)h;
+    }
+    ~Stream() {   // idle by then
+        if (s && masked && keep) g_streams.give(key, s);
+        else if (s && masked) (void)sdr_stream_destroy(s);
+        else if (s) (void)hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+};
+
+struct Ctx : NoCopy {
+    sdr_ctx* c = nullptr;
+    std::array<int, 5> key{};
+    bool keep = false;
+    // a pooled context comes back in the reference's initial state (sdr_ctx_reset)
+    void take(int device, int nch, int mode, int rds_on, int flags, bool cache) {
+        key = {device, nch, mode, rds_on, flags};
+        keep = cache;
+        if (g_ctxs.take(key, &c)) check_sdr(sdr_ctx_reset(c, nullptr), "sdr_ctx_reset");
+        else check_sdr(sdr_ctx_create(&c, device, nch, mode, rds_on, flags), "sdr_ctx_create");
+    }
+    ~Ctx() {   // after the run's streams have drained
+        if (c && keep) g_ctxs.give(key, c);
+        else if (c) sdr_ctx_destroy(c);
+    }
+    operator sdr_ctx*() const { return c; }
+};
+
+template <typename T>
+struct Pinned : NoCopy {
+    T* p = nullptr;
+    size_t bytes = 0;
+    bool keep = false;
+    void take(size_t n, bool cache) {
+        bytes = n;
+        keep = cache;
+        void* v = nullptr;
+        if (!g_pinned.take(n, &v)) check_hip(hipHostMalloc(&v, n, hipHostMallocDefault), "hipHostMalloc");
+        p = static_cast<T*>(v);
+    }
+    ~Pinned() {
+        if (p && keep) g_pinned.give(bytes, p);
+        else if (p) (void)hipHostFree(p);
+    }
+    operator T*() const { return p; }
+};
 
 // ------------------------------------------------------------------ reader: input -> pinned ring
 struct Reader {
@@ -169,34 +260,28 @@ struct Reader {
     FILE* f = nullptr;
     size_t bytes = 0;
     uint8_t* slot[SLOTS] = {};
-    hipEvent_t consumed[SLOTS] = {};    // the H2D copy out of the slot has completed
+    Event consumed[SLOTS];              // the H2D copy out of the slot has completed
     bool armed[SLOTS] = {};
     std::mutex m;
     std::condition_variable cv;
     std::deque<int> filled, empty;
     bool eof = false;
     double read_s = 0.0;                // time spent reading (the input side of the I/O)
-    int readers = 8;                    // pread threads per block (regular files; SDR_MULTI_READERS)
+    int readers = 1;                    // pread threads per block (regular files)
     long long file_size = 0, offset = 0;
     std::thread th;
 
-    Reader(const std::string& path, size_t block_bytes) : bytes(block_bytes) {
+    Reader(const std::string& path, size_t block_bytes, int file_readers) : bytes(block_bytes) {
         f = path == "-" ? stdin : std::fopen(path.c_str(), "rb");
         if (!f) die("cannot open " + path);
-        if (f != stdin) {   // a regular file is read by several threads at once (pread of a block's parts)
-            struct stat sb;
-            if (fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
-                file_size = (long long)sb.st_size;
-                if (const char* e = std::getenv("SDR_MULTI_READERS")) readers = std::max(1, std::atoi(e));
-            } else {
-                readers = 1;
-            }
-        } else {
-            readers = 1;
+        struct stat sb;   // a regular file is read by several threads at once (pread of a block's parts)
+        if (f != stdin && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
+            file_size = (long long)sb.st_size;
+            readers = file_readers;
         }
         for (int i = 0; i < SLOTS; i++) {
             check_hip(hipHostMalloc(reinterpret_cast<void**>(&slot[i]), bytes, hipHostMallocDefault), "hipHostMalloc");
-            consumed[i] = new_event();
+            consumed[i].make();
             empty.push_back(i);
         }
         th = std::thread([this] { run(); });
@@ -278,13 +363,38 @@ struct Reader {
 // (LAG 1 measured 0.70-0.81 ms per block against 0.687 for the same GPU work in one thread, bench.py)
 constexpr int LAG = 2, NH = LAG + 1;   // pinned output buffers in rotation
 struct AudioRes {
-    hipEvent_t pre = nullptr, pll = nullptr, post = nullptr, out_ready[NH] = {}, d0[NH] = {}, d1[NH] = {};
-    int16_t *d_lr[2] = {}, *h_lr[NH] = {};
+    Event pre, pll, out_ready[NH], d0[NH], d1[NH];
+    DevBuf<int16_t> d_lr[2];
+    Pinned<int16_t> h_lr[NH];
+    AudioRes(size_t lr_bytes, bool cache) {
+        pre.make();
+        pll.make();
+        for (auto& d : d_lr) d.get(lr_bytes / sizeof(int16_t));
+        for (int h = 0; h < NH; h++) {
+            out_ready[h].make();
+            d0[h].make_timing();
+            d1[h].make_timing();
+            h_lr[h].take(lr_bytes, cache);
+        }
+    }
 };
 struct RdsRes {
-    hipEvent_t pre = nullptr, pll = nullptr, out_ready[NH] = {};
-    int32_t *d_nbits = nullptr, *h_nbits[NH] = {};
-    uint8_t *d_bits = nullptr, *h_bits[NH] = {};
+    Event pre, pll, out_ready[NH];
+    DevBuf<int32_t> d_nbits;
+    DevBuf<uint8_t> d_bits;
+    Pinned<int32_t> h_nbits[NH];
+    Pinned<uint8_t> h_bits[NH];
+    RdsRes(int nch, bool cache) {
+        pre.make();
+        pll.make();
+        d_nbits.get((size_t)nch);
+        d_bits.get((size_t)nch * SDR_MAX_BITS);
+        for (int h = 0; h < NH; h++) {
+            out_ready[h].make();
+            h_nbits[h].take(nch * sizeof(int32_t), cache);
+            h_bits[h].take((size_t)nch * SDR_MAX_BITS, cache);
+        }
+    }
 };
 
 // A metered run's host side. Each consumer copies the meter's rows out after its own call and takes
@@ -295,8 +405,8 @@ struct MeterOut {
     sdr_meter* m = nullptr;
     sdr_meter_opts mo{};
     int nch = 0, mode = 0;
-    uint8_t* h_rows[2][LAG + 1] = {};    // pinned, per consumer and rotation slot: nch rows
-    FILE* f = nullptr;                   // PREFIX.meter
+    Pinned<uint8_t> h_rows[2][NH];       // per consumer and rotation slot: nch rows
+    File f;                              // PREFIX.meter
     std::mutex mu;
     std::deque<std::pair<long long, std::vector<sdr_meter_row>>> pending[2];
     long long blocks = 0;
@@ -305,10 +415,24 @@ struct MeterOut {
         long long flag[4] = {};          // blocks with STEREO, RDS, OFFTUNE, DEAD_AIR
     };
     std::vector<Sum> sum;
-    // consumer `which` (0 audio, 1 RDS) hands in its copy of block blk's rows
-    void part(long long blk, int which, const uint8_t* rows) {
+    MeterOut(const sdr_multi_opts& o, const sdr_meter_opts& opts, bool cache) : mo(opts), nch(o.nch), mode(o.mode), sum((size_t)o.nch) {
+        check_sdr(sdr_meter_create(&m, o.device, o.nch, o.mode), "sdr_meter_create");
+        for (auto& per : h_rows)
+            for (auto& p : per) p.take((size_t)nch * sizeof(sdr_meter_row), cache);
+        if (o.out_prefix) f.open(std::string(o.out_prefix) + ".meter", "wb");
+    }
+    ~MeterOut() { (void)sdr_meter_destroy(m); }
+    // consumer `which` (0 audio, 1 RDS), behind its meter call on s: the rows into its rotation slot h
+    void copy_out(int which, int h, hipStream_t s) {
+        const sdr_meter_row* d_rows = nullptr;
+        check_sdr(sdr_meter_rows(m, &d_rows), "sdr_meter_rows");
+        check_hip(hipMemcpyAsync(h_rows[which][h], d_rows, (size_t)nch * sizeof(sdr_meter_row), hipMemcpyDeviceToHost, s),
+                  "hipMemcpyAsync");
+    }
+    // consumer `which` hands in its copy of block blk's rows, once the copy into slot h has completed
+    void part(long long blk, int which, int h) {
         std::vector<sdr_meter_row> mine((size_t)nch);
-        std::memcpy(mine.data(), rows, (size_t)nch * sizeof(sdr_meter_row));
+        std::memcpy(mine.data(), h_rows[which][h], (size_t)nch * sizeof(sdr_meter_row));
         std::lock_guard<std::mutex> lk(mu);
         auto& other = pending[which ^ 1];
         if (other.empty() || other.front().first != blk) {   // (both hand their blocks in ascending order)
@@ -339,8 +463,8 @@ struct MeterOut {
     }
     // PREFIX.status: per channel the run's means and the flags that held on more than half the blocks
     void write_status(const std::string& path) const {
-        FILE* t = std::fopen(path.c_str(), "w");
-        if (!t) die("cannot write " + path);
+        File t;
+        t.open(path, "w");
         static const char* names[4] = {"STEREO", "RDS", "OFFTUNE", "DEAD_AIR"};
         for (int c = 0; c < nch; c++) {
             const Sum& s = sum[(size_t)c];
@@ -355,7 +479,6 @@ struct MeterOut {
                 }
             std::fprintf(t, "%s\n", any ? "" : " -");
         }
-        std::fclose(t);
     }
 };
 
@@ -363,32 +486,88 @@ struct MeterOut {
 struct AudioFin {
     sdr_audio* a = nullptr;
     bool blend = false;                  // the blend targets follow the meter's rows
-    int16_t *d_out[2] = {}, *h_out[LAG + 1] = {};
-    FILE* f = nullptr;                   // PREFIX.audio
+    DevBuf<int16_t> d_out[2];
+    Pinned<int16_t> h_out[NH];
+    File f;                              // PREFIX.audio
+    AudioFin(const sdr_multi_opts& o, const sdr_audio_opts& ao, bool blend_, size_t lr_bytes, bool cache) : blend(blend_) {
+        check_sdr(sdr_audio_create(&a, o.device, o.nch, o.mode, 2, &ao), "sdr_audio_create");
+        check_sdr(sdr_audio_reset(a, nullptr), "sdr_audio_reset");   // (synchronised with the batches, before the threads start)
+        for (auto& d : d_out) d.get(lr_bytes / sizeof(int16_t));
+        for (auto& p : h_out) p.take(lr_bytes, cache);
+        if (o.out_prefix) f.open(std::string(o.out_prefix) + ".audio", "wb");
+    }
+    ~AudioFin() { (void)sdr_audio_destroy(a); }
 };
 
-struct Shared {
+// A wide run's splitter and its geometry: nwide * (2 W - 1) capture rows per block from rows of 2 * wide_iq bytes
+struct Splitter {
+    sdr_split* s = nullptr;
+    int rows = 0, wide_iq = 0;
+    Splitter(const sdr_multi_opts& o, const sdr_multi_wide& w) {
+        check_sdr(sdr_split_geometry(o.mode, w.W, &rows, nullptr, &wide_iq, nullptr, nullptr), "sdr_split_geometry");
+        rows *= w.nwide;
+        check_sdr(sdr_split_create(&s, o.device, o.mode, w.W, w.nwide, w.shift), "sdr_split_create");
+    }
+    ~Splitter() { (void)sdr_split_destroy(s); }
+};
+
+// a recycled device batch of fm_demod [nch][block_if] and its events (include/dropin/fm_batch.h)
+struct Batch {
+    FmBatch fb;
+    DevBuf<float> d_fm;
+    Event ready, released[2];
+    Batch(int nch, int n) {
+        fb.nch = nch;
+        fb.n = n;
+        fb.stride = (size_t)(n + 63) / 64 * 64;
+        fb.d_fm = d_fm.get(fb.stride * nch);
+        ready.make();
+        fb.ready = ready;
+        for (int i = 0; i < 2; i++) {
+            released[i].make();
+            fb.released[i] = released[i];
+            check_hip(hipEventRecord(released[i], nullptr), "hipEventRecord");   // trivially complete
+        }
+    }
+};
+
+struct Trace {   // SDR_MULTI_TRACE=1: a phase's end, in host time since the call
+    bool on = false;
+    std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
+    void operator()(const char* what) const {
+        if (on)
+            std::fprintf(stderr, "sdr_multi: %-16s %8.2f ms\n", what,
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
+    }
+};
+
+// What the three threads share. Members are released in the reverse of this order: the streams and the
+// contexts last.
+struct Shared : NoCopy {
+    explicit Shared(const Switches& s) : sw(s) {}
     sdr_multi_opts o{};
-    MeterOut* meter = nullptr;           // a metered run (sdr_multi_run_metered)
-    AudioFin* fin = nullptr;             // a finished run (sdr_multi_run_finished)
+    const Switches sw;
     int rows = 0;                        // input rows per block: nch, a tuned run's nsrc, a wide run's nwide
     bool tuned = false;
-    sdr_split* split = nullptr;          // a wide run (sdr_multi_run_wide): the input rows are wide int8 streams
     size_t in_row = 0;                   // bytes of an input row: 2*block_iq, or a wide run's 2*W*block_iq
-    int split_rows = 0;                  // a wide run's capture rows per block, nwide * (2 W - 1)
-    AudioRes ar;
-    RdsRes rr;
-    hipStream_t s_d2h = nullptr;         // the L/R copies when not on s_post (SDR_MULTI_D2H=copy)
     sdr_info info{};
-    ThreadSafeQueue<FmBatch*> q;
-    sdr_ctx* ctx[3] = {};                // RF, audio, RDS (each thread owns its context)
-    hipStream_t s_fe = nullptr, s_post = nullptr, s_pll[2] = {}, s_copy = nullptr;
-    hipStream_t s_post_c[2] = {};        // consumer i's post stream: s_post, or its own (SDR_MULTI_POSTS=2)
+    // s_fe, s_post, s_pll: the header comment's streams; s_post2: the RDS consumer's own post stream
+    // (SDR_MULTI_POSTS=2); s_copy: the uploads of a byte-stream input
+    Stream s_fe, s_post, s_post2, s_pll[2], s_copy;
+    hipStream_t s_post_c[2] = {};        // consumer i's post stream: s_post, or s_post2
     // persistent mode: a stream over every CU for the first block's front-end side and the last
     // block's post side (the PLL CUs idle then, as bench.py's fill and drain stream), and the events
     // that order the switches (RF, audio, RDS)
-    hipStream_t s_all = nullptr;
-    hipEvent_t ev_first[3] = {}, ev_last[3] = {};
+    Stream s_all;
+    Event ev_first[3], ev_last[3];
+    Ctx ctx[3];                          // RF, audio, RDS (each thread owns its context)
+    std::optional<Splitter> split;       // a wide run: the input rows are wide int8 streams
+    std::optional<AudioRes> ar;
+    std::optional<RdsRes> rr;
+    std::optional<MeterOut> meter;       // a metered run
+    std::optional<AudioFin> fin;         // a finished run
+    ThreadSafeQueue<FmBatch*> q;
+    std::deque<Batch> batches;
     // the threads start before the clock: each makes its first runtime calls (per-thread HIP state),
     // reports ready and waits for the go
     std::mutex start_mu;
@@ -399,7 +578,6 @@ struct Shared {
     // block 1 pre parts behind block 0's (consumer_pll), so that it runs after block 0's pre parts
     // instead of beside them -- those start the PLLs (SDR_MULTI_FILL=0: no such wait, round 6's first
     // engine; profiles/r06/queue_fill/)
-    bool fill_gate = true;
     int first_pre = 0;
     void arrive_and_wait() {
         (void)hipStreamQuery(s_fe);
@@ -417,9 +595,9 @@ struct Shared {
 
 // block b's front-end-side stream (the all-CU stream for the first block) and consumer i's post stream
 // (the all-CU stream for the last block)
-hipStream_t fe_stream(const Shared* sh, long long b) { return (sh->s_all && b == 0) ? sh->s_all : sh->s_fe; }
+hipStream_t fe_stream(const Shared* sh, long long b) { return (sh->s_all.s && b == 0) ? sh->s_all.s : sh->s_fe.s; }
 hipStream_t post_stream(const Shared* sh, int i, long long b) {
-    return (sh->s_all && b == sh->nblocks_known - 1) ? sh->s_all : sh->s_post_c[i];
+    return (sh->s_all.s && b == sh->nblocks_known - 1) ? sh->s_all.s : sh->s_post_c[i];
 }
 // work enqueued on `to` from now on follows the work enqueued on `from` so far
 void follow(hipStream_t to, hipStream_t from, hipEvent_t ev) {
@@ -429,13 +607,8 @@ void follow(hipStream_t to, hipStream_t from, hipEvent_t ev) {
 
 // the host waits for a block's outputs by polling the event (yielding between polls) rather than
 // hipEventSynchronize, so a waiting consumer thread never sits inside the runtime while the other
-// threads enqueue the next blocks (SDR_MULTI_SYNC=event: hipEventSynchronize, for A/B)
-bool g_poll_events = true;
+// threads enqueue the next blocks
 void wait_event(hipEvent_t e) {
-    if (!g_poll_events) {
-        check_hip(hipEventSynchronize(e), "hipEventSynchronize");
-        return;
-    }
     for (;;) {
         const hipError_t r = hipEventQuery(e);
         if (r == hipSuccess) return;
@@ -444,11 +617,6 @@ void wait_event(hipEvent_t e) {
     }
 }
 
-hipEvent_t timing_event() {
-    hipEvent_t e = nullptr;
-    check_hip(hipEventCreate(&e), "hipEventCreate");
-    return e;
-}
 float elapsed_ms(hipEvent_t a, hipEvent_t b) {
     wait_event(b);
     float ms = 0.0f;
@@ -466,12 +634,12 @@ void rf_thread(Shared* sh) {
     const size_t row = 2 * (size_t)in.block_iq, bytes = sh->in_row * (size_t)sh->rows;
     hipStream_t s = sh->s_fe;
     const bool dev_in = o.in_path == nullptr;
-    uint8_t* d_iq[2] = {};
-    hipEvent_t h2d[2] = {}, fe_done[2] = {};
+    DevBuf<uint8_t> d_iq[2];
+    Event h2d[2], fe_done[2];
     // copy timing: a ring of event pairs, read without blocking the producer (a pair is waited for
     // only when the ring wraps onto a copy that has not finished)
     constexpr int TR = 8;
-    hipEvent_t c0[TR] = {}, c1[TR] = {};
+    Event c0[TR], c1[TR];
     long long timed = 0;                                    // blocks whose copy time is in h2d_ms
     auto harvest = [&](long long upto, bool wait) {
         for (; timed < upto; timed++) {
@@ -483,22 +651,25 @@ void rf_thread(Shared* sh) {
     // a wide run: two buffers of capture rows. Block b's splitter writes buffer b & 1 on the block's
     // front-end stream, in front of the front end that reads it; block b + 2 may be on another stream
     // than block b (the first block's all-CU stream), so its splitter waits for rows_done of block b.
-    uint8_t* d_rows[2] = {};
-    hipEvent_t rows_done[2] = {};
+    DevBuf<uint8_t> d_rows[2];
+    Event rows_done[2];
     if (sh->split)
         for (int k = 0; k < 2; k++) {
-            check_hip(hipMalloc(reinterpret_cast<void**>(&d_rows[k]), row * (size_t)sh->split_rows), "hipMalloc");
-            rows_done[k] = new_event();
+            d_rows[k].get(row * (size_t)sh->split->rows);
+            rows_done[k].make();
         }
-    Reader* rd = nullptr;
+    std::optional<Reader> rd;
     if (!dev_in) {
         for (int k = 0; k < 2; k++) {
-            check_hip(hipMalloc(reinterpret_cast<void**>(&d_iq[k]), bytes), "hipMalloc");
-            h2d[k] = new_event();
-            fe_done[k] = new_event();
+            d_iq[k].get(bytes);
+            h2d[k].make();
+            fe_done[k].make();
         }
-        for (int i = 0; i < TR; i++) { c0[i] = timing_event(); c1[i] = timing_event(); }
-        rd = new Reader(o.in_path, bytes);
+        for (int i = 0; i < TR; i++) {
+            c0[i].make_timing();
+            c1[i].make_timing();
+        }
+        rd.emplace(o.in_path, bytes, sh->sw.readers);
     }
     for (long long b = 0;; b++) {
         const uint8_t* src = nullptr;
@@ -516,14 +687,14 @@ void rf_thread(Shared* sh) {
             harvest(b, false);
             const int t = (int)(b % TR);
             check_hip(hipEventRecord(c0[t], sh->s_copy), "hipEventRecord");
-            check_hip(hipMemcpyAsync(d_iq[k], rd->slot[slot], bytes, hipMemcpyHostToDevice, sh->s_copy), "hipMemcpyAsync");
+            check_hip(hipMemcpyAsync(d_iq[k].p, rd->slot[slot], bytes, hipMemcpyHostToDevice, sh->s_copy), "hipMemcpyAsync");
             check_hip(hipEventRecord(c1[t], sh->s_copy), "hipEventRecord");
             check_hip(hipEventRecord(h2d[k], sh->s_copy), "hipEventRecord");
             rd->release(slot, sh->s_copy);
             check_hip(hipStreamWaitEvent(s, h2d[k], 0), "hipStreamWaitEvent");
-            src = d_iq[k];
+            src = d_iq[k].p;
         }
-        if (b == 1 && sh->s_all && sh->fill_gate) {   // after both consumers' block 0 pre parts (Shared)
+        if (b == 1 && sh->s_all.s && sh->sw.fill) {   // after both consumers' block 0 pre parts (Shared)
             std::unique_lock<std::mutex> lk(sh->start_mu);
             sh->start_cv.wait(lk, [sh] { return sh->first_pre == 2; });
         }
@@ -533,9 +704,9 @@ void rf_thread(Shared* sh) {
         if (sh->split) {
             const int k = (int)(b & 1);
             if (b >= 2) check_hip(hipStreamWaitEvent(sf, rows_done[k], 0), "hipStreamWaitEvent");
-            check_sdr(sdr_split_block(sh->split, reinterpret_cast<const int8_t*>(src), stride, d_rows[k], row, sf),
+            check_sdr(sdr_split_block(sh->split->s, reinterpret_cast<const int8_t*>(src), stride, d_rows[k].p, row, sf),
                       "sdr_split_block");
-            check_sdr(sdr_frontend_tuned(ctx, d_rows[k], row, sf), "sdr_frontend_tuned");
+            check_sdr(sdr_frontend_tuned(ctx, d_rows[k].p, row, sf), "sdr_frontend_tuned");
             check_hip(hipEventRecord(rows_done[k], sf), "hipEventRecord");
         } else if (sh->tuned) check_sdr(sdr_frontend_tuned(ctx, src, stride, sf), "sdr_frontend_tuned");
         else check_sdr(sdr_frontend(ctx, src, stride, sf), "sdr_frontend");
@@ -550,17 +721,10 @@ void rf_thread(Shared* sh) {
         sh->blocks = b + 1;
     }
     sh->q.push(nullptr);                                    // end of stream
-    check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
-    for (int k = 0; k < 2 && sh->split; k++) {
-        (void)hipFree(d_rows[k]);
-        (void)hipEventDestroy(rows_done[k]);
-    }
+    check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");   // before this thread's buffers go
     if (!dev_in) {
         harvest(sh->blocks, true);
         sh->read_s = rd->read_s;
-        delete rd;
-        for (auto& p : d_iq) (void)hipFree(p);
-        for (int i = 0; i < TR; i++) { (void)hipEventDestroy(c0[i]); (void)hipEventDestroy(c1[i]); }
     }
 }
 
@@ -601,6 +765,20 @@ void consumer_pll(Shared* sh, sdr_ctx* ctx, int indicator, hipEvent_t pre, hipEv
     check_hip(hipStreamWaitEvent(sh->s_post_c[indicator], pll, 0), "hipStreamWaitEvent");
 }
 
+// a consumer's loop: enqueue block b's work, then handle on the host the outputs of block b - LAG (the
+// rotation over NH slots); at the end of the stream the last LAG blocks, and the consumer's streams drain
+template <typename Enqueue, typename Handle>
+void consumer_loop(Shared* sh, sdr_ctx* ctx, int indicator, Enqueue enqueue, Handle handle) {
+    long long b = 0;
+    for (; consume(sh, ctx, indicator); b++) {
+        enqueue(b);
+        if (b >= LAG) handle(b - LAG);                      // overlaps the GPU work of blocks b-1, b
+    }
+    for (long long blk = std::max(0LL, b - LAG); blk < b; blk++) handle(blk);
+    for (hipStream_t x : {sh->s_post_c[indicator], sh->s_all.s})
+        if (x) check_hip(hipStreamSynchronize(x), "hipStreamSynchronize");
+}
+
 // ------------------------------------------------------------------ audio (consumer 0)
 void audio_thread(Shared* sh) {
     const sdr_multi_opts& o = sh->o;
@@ -608,62 +786,44 @@ void audio_thread(Shared* sh) {
     sh->arrive_and_wait();
     sdr_ctx* ctx = sh->ctx[1];
     const size_t n = 2 * (size_t)sh->info.n_audio, bytes = n * o.nch * sizeof(int16_t);
-    AudioRes& r = sh->ar;
-    FILE* f = nullptr;
-    if (o.out_prefix) {
-        f = std::fopen((std::string(o.out_prefix) + ".pcm").c_str(), "wb");
-        if (!f) die(std::string("cannot write ") + o.out_prefix + ".pcm");
-    }
-    long long b = 0;
+    AudioRes& r = *sh->ar;
+    MeterOut* mt = sh->meter ? &*sh->meter : nullptr;
+    AudioFin* af = sh->fin ? &*sh->fin : nullptr;
+    File f;
+    if (o.out_prefix) f.open(std::string(o.out_prefix) + ".pcm", "wb");
+    auto enqueue = [&](long long b) {
+        const int k = (int)(b & 1), h = (int)(b % NH);
+        check_sdr(sdr_stereo_pre(ctx, fe_stream(sh, b)), "sdr_stereo_pre");
+        consumer_pll(sh, ctx, 0, r.pre, r.pll, b);
+        const hipStream_t s = post_stream(sh, 0, b);
+        // d_lr[k] is free: block b-2's copy out of it precedes on the post stream
+        check_sdr(sdr_stereo_post(ctx, r.d_lr[k].p, n, s), "sdr_stereo_post");
+        if (mt) {
+            check_sdr(sdr_meter_audio(mt->m, ctx, r.d_lr[k].p, n, s), "sdr_meter_audio");
+            mt->copy_out(0, h, s);
+        }
+        if (af) {   // d_out[k] is free as d_lr[k] is: its copy of block b-2 precedes out_ready
+            if (af->blend) check_sdr(sdr_audio_blend_from_meter(af->a, mt->m, s), "sdr_audio_blend_from_meter");
+            check_sdr(sdr_audio_finish(af->a, r.d_lr[k].p, n, af->d_out[k].p, n, s), "sdr_audio_finish");
+        }
+        check_hip(hipEventRecord(r.d0[h], s), "hipEventRecord");
+        check_hip(hipMemcpyAsync(r.h_lr[h], r.d_lr[k].p, bytes, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+        check_hip(hipEventRecord(r.d1[h], s), "hipEventRecord");
+        if (af) check_hip(hipMemcpyAsync(af->h_out[h], af->d_out[k].p, bytes, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+        check_hip(hipEventRecord(r.out_ready[h], s), "hipEventRecord");
+    };
     auto write_block = [&](long long blk) {   // stereo.cpp:111, for every channel
         const int h = (int)(blk % NH);
         wait_event(r.out_ready[h]);
         sh->d2h_ms += elapsed_ms(r.d0[h], r.d1[h]);
-        if (sh->meter) sh->meter->part(blk, 0, sh->meter->h_rows[0][h]);
+        if (mt) mt->part(blk, 0, h);
         if (f) std::fwrite(r.h_lr[h], 1, bytes, f);
-        if (sh->fin && sh->fin->f && std::fwrite(sh->fin->h_out[h], 1, bytes, sh->fin->f) != bytes)
-            die("cannot write the .audio file");
+        if (af && af->f && std::fwrite(af->h_out[h], 1, bytes, af->f) != bytes) die("cannot write the .audio file");
         if (o.cap_lr && blk < o.cap_blocks)
             for (int i = 0; i < o.ncap; i++)
-                std::memcpy(o.cap_lr + ((size_t)blk * o.ncap + i) * n, r.h_lr[h] + (size_t)o.cap_ch[i] * n,
-                            n * sizeof(int16_t));
+                std::memcpy(o.cap_lr + ((size_t)blk * o.ncap + i) * n, r.h_lr[h].p + (size_t)o.cap_ch[i] * n, n * sizeof(int16_t));
     };
-    while (consume(sh, ctx, 0)) {
-        const int k = (int)(b & 1), h = (int)(b % NH);
-        check_sdr(sdr_stereo_pre(ctx, fe_stream(sh, b)), "sdr_stereo_pre");
-        consumer_pll(sh, ctx, 0, r.pre, r.pll, b);
-        const hipStream_t s = post_stream(sh, 0, b), sc = sh->s_d2h ? sh->s_d2h : s;
-        // d_lr[k] is free once block b-2's copy out of it is done (same stream, or the copy stream's event)
-        if (sc != s && b >= 2) check_hip(hipStreamWaitEvent(s, r.out_ready[(b - 2) % NH], 0), "hipStreamWaitEvent");
-        check_sdr(sdr_stereo_post(ctx, r.d_lr[k], n, s), "sdr_stereo_post");
-        if (MeterOut* mt = sh->meter) {
-            const sdr_meter_row* d_rows = nullptr;
-            check_sdr(sdr_meter_audio(mt->m, ctx, r.d_lr[k], n, s), "sdr_meter_audio");
-            check_sdr(sdr_meter_rows(mt->m, &d_rows), "sdr_meter_rows");
-            check_hip(hipMemcpyAsync(mt->h_rows[0][h], d_rows, (size_t)o.nch * sizeof(sdr_meter_row), hipMemcpyDeviceToHost, s),
-                      "hipMemcpyAsync");
-        }
-        AudioFin* af = sh->fin;
-        if (af) {   // d_out[k] is free as d_lr[k] is: its copy of block b-2 precedes out_ready
-            if (af->blend) check_sdr(sdr_audio_blend_from_meter(af->a, sh->meter->m, s), "sdr_audio_blend_from_meter");
-            check_sdr(sdr_audio_finish(af->a, r.d_lr[k], n, af->d_out[k], n, s), "sdr_audio_finish");
-        }
-        if (sc != s) {
-            check_hip(hipEventRecord(r.post, s), "hipEventRecord");
-            check_hip(hipStreamWaitEvent(sc, r.post, 0), "hipStreamWaitEvent");
-        }
-        check_hip(hipEventRecord(r.d0[h], sc), "hipEventRecord");
-        check_hip(hipMemcpyAsync(r.h_lr[h], r.d_lr[k], bytes, hipMemcpyDeviceToHost, sc), "hipMemcpyAsync");
-        check_hip(hipEventRecord(r.d1[h], sc), "hipEventRecord");
-        if (af) check_hip(hipMemcpyAsync(af->h_out[h], af->d_out[k], bytes, hipMemcpyDeviceToHost, sc), "hipMemcpyAsync");
-        check_hip(hipEventRecord(r.out_ready[h], sc), "hipEventRecord");
-        if (b >= LAG) write_block(b - LAG);                 // overlaps the GPU work of blocks b-1, b
-        b++;
-    }
-    for (long long blk = std::max(0LL, b - LAG); blk < b; blk++) write_block(blk);
-    if (f) std::fclose(f);
-    for (hipStream_t x : {sh->s_post_c[0], sh->s_d2h, sh->s_all})
-        if (x) check_hip(hipStreamSynchronize(x), "hipStreamSynchronize");
+    consumer_loop(sh, ctx, 0, enqueue, write_block);
 }
 
 // ------------------------------------------------------------------ RDS (consumer 1)
@@ -682,28 +842,43 @@ void rds_thread(Shared* sh) {
     check_hip(hipSetDevice(o.device), "hipSetDevice");
     sh->arrive_and_wait();
     sdr_ctx* ctx = sh->ctx[2];
-    RdsRes& r = sh->rr;
-    hipEvent_t pre = r.pre, pll = r.pll, *out_ready = r.out_ready;   // [NH]
-    int32_t *d_nbits = r.d_nbits, **h_nbits = r.h_nbits;
-    uint8_t *d_bits = r.d_bits, **h_bits = r.h_bits;
+    RdsRes& r = *sh->rr;
+    MeterOut* mt = sh->meter ? &*sh->meter : nullptr;
     std::vector<FrameState> fs((size_t)o.nch);
+    auto enqueue = [&](long long b) {
+        const int k = (int)(b % NH);
+        check_sdr(sdr_rds_pre(ctx, fe_stream(sh, b)), "sdr_rds_pre");
+        consumer_pll(sh, ctx, 1, r.pre, r.pll, b);
+        const hipStream_t s = post_stream(sh, 1, b);
+        check_sdr(sdr_rds_post(ctx, nullptr, 0, s), "sdr_rds_post");
+        if (mt) {
+            check_sdr(sdr_meter_rds(mt->m, ctx, s), "sdr_meter_rds");
+            mt->copy_out(1, k, s);
+        }
+        check_sdr(sdr_rds_bits(ctx, nullptr, nullptr, nullptr, 0, r.d_nbits.p, r.d_bits.p, SDR_MAX_BITS, s), "sdr_rds_bits");
+        check_hip(hipMemcpyAsync(r.h_nbits[k], r.d_nbits.p, o.nch * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+        check_hip(hipMemcpyAsync(r.h_bits[k], r.d_bits.p, (size_t)o.nch * SDR_MAX_BITS, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+        check_hip(hipEventRecord(r.out_ready[k], s), "hipEventRecord");
+    };
     auto frame_layer = [&](long long blk) {   // rds.cpp:181-189 per channel; parse() prints to cerr
         const int k = (int)(blk % NH);
-        wait_event(out_ready[k]);
-        if (sh->meter) sh->meter->part(blk, 1, sh->meter->h_rows[1][k]);
+        const int32_t* h_nbits = r.h_nbits[k];
+        const uint8_t* h_bits = r.h_bits[k];
+        wait_event(r.out_ready[k]);
+        if (mt) mt->part(blk, 1, k);
         if (o.cap_nbits && blk < o.cap_blocks)
             for (int i = 0; i < o.ncap; i++) {
-                o.cap_nbits[(size_t)blk * o.ncap + i] = h_nbits[k][o.cap_ch[i]];
-                std::memcpy(o.cap_bits + ((size_t)blk * o.ncap + i) * SDR_MAX_BITS,
-                            h_bits[k] + (size_t)o.cap_ch[i] * SDR_MAX_BITS, SDR_MAX_BITS);
+                o.cap_nbits[(size_t)blk * o.ncap + i] = h_nbits[o.cap_ch[i]];
+                std::memcpy(o.cap_bits + ((size_t)blk * o.ncap + i) * SDR_MAX_BITS, h_bits + (size_t)o.cap_ch[i] * SDR_MAX_BITS,
+                            SDR_MAX_BITS);
             }
         if (!o.out_prefix) return;
         std::streambuf* saved = std::cerr.rdbuf();
         for (int c = 0; c < o.nch; c++) {
-            const int nb = h_nbits[k][c];
+            const int nb = h_nbits[c];
             if (nb < 0) continue;                       // block_count <= 5 (rds.cpp:135)
             FrameState& st = fs[(size_t)c];
-            const uint8_t* bits = h_bits[k] + (size_t)c * SDR_MAX_BITS;
+            const uint8_t* bits = h_bits + (size_t)c * SDR_MAX_BITS;
             st.decoder_cont++;
             st.stream.insert(st.stream.end(), bits, bits + nb);
             if (st.decoder_cont == 15) {
@@ -719,120 +894,13 @@ void rds_thread(Shared* sh) {
             }
         }
     };
-    long long b = 0;
-    while (consume(sh, ctx, 1)) {
-        const int k = (int)(b % NH);
-        check_sdr(sdr_rds_pre(ctx, fe_stream(sh, b)), "sdr_rds_pre");
-        consumer_pll(sh, ctx, 1, pre, pll, b);
-        const hipStream_t s = post_stream(sh, 1, b);
-        check_sdr(sdr_rds_post(ctx, nullptr, 0, s), "sdr_rds_post");
-        if (MeterOut* mt = sh->meter) {
-            const sdr_meter_row* d_rows = nullptr;
-            check_sdr(sdr_meter_rds(mt->m, ctx, s), "sdr_meter_rds");
-            check_sdr(sdr_meter_rows(mt->m, &d_rows), "sdr_meter_rows");
-            check_hip(hipMemcpyAsync(mt->h_rows[1][k], d_rows, (size_t)o.nch * sizeof(sdr_meter_row), hipMemcpyDeviceToHost, s),
-                      "hipMemcpyAsync");
-        }
-        check_sdr(sdr_rds_bits(ctx, nullptr, nullptr, nullptr, 0, d_nbits, d_bits, SDR_MAX_BITS, s), "sdr_rds_bits");
-        check_hip(hipMemcpyAsync(h_nbits[k], d_nbits, o.nch * sizeof(int32_t), hipMemcpyDeviceToHost, s),
-                  "hipMemcpyAsync");
-        check_hip(hipMemcpyAsync(h_bits[k], d_bits, (size_t)o.nch * SDR_MAX_BITS, hipMemcpyDeviceToHost, s),
-                  "hipMemcpyAsync");
-        check_hip(hipEventRecord(out_ready[k], s), "hipEventRecord");
-        if (b >= LAG) frame_layer(b - LAG);
-        b++;
-    }
-    for (long long blk = std::max(0LL, b - LAG); blk < b; blk++) frame_layer(blk);
-    if (o.out_prefix) {
-        FILE* f = std::fopen((std::string(o.out_prefix) + ".rds").c_str(), "w");
-        if (!f) die(std::string("cannot write ") + o.out_prefix + ".rds");
-        for (int c = 0; c < o.nch; c++) {
-            std::istringstream lines(fs[(size_t)c].text);
-            for (std::string line; std::getline(lines, line);) std::fprintf(f, "ch %d: %s\n", c, line.c_str());
-        }
-        std::fclose(f);
-    }
-    for (hipStream_t x : {sh->s_post_c[1], sh->s_all})
-        if (x) check_hip(hipStreamSynchronize(x), "hipStreamSynchronize");
-}
-
-// pinned host buffers outlive a run: a process that runs the receiver again (a server taking one input
-// after another, bench.py's timed second run) reuses them instead of pinning ~25 MB anew, which took
-// ~50 ms in which the GPU sat idle and its clock fell (profiles/r06/queue_fill/). Held until the
-// process exits; SDR_MULTI_PIN_CACHE=0: allocated and freed per run.
-std::mutex g_pin_mu;
-std::vector<std::pair<size_t, void*>> g_pin_free;
-bool pin_cache_on() {
-    const char* e = std::getenv("SDR_MULTI_PIN_CACHE");
-    return !e || std::atoi(e) != 0;
-}
-template <typename T>
-void pinned_get(T** p, size_t bytes) {
-    if (pin_cache_on()) {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        for (size_t i = 0; i < g_pin_free.size(); i++)
-            if (g_pin_free[i].first == bytes) {
-                *p = static_cast<T*>(g_pin_free[i].second);
-                g_pin_free.erase(g_pin_free.begin() + (long)i);
-                return;
-            }
-    }
-    check_hip(hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocDefault), "hipHostMalloc");
-}
-void pinned_put(void* p, size_t bytes) {
-    if (!p) return;
-    if (!pin_cache_on()) {
-        (void)hipHostFree(p);
-        return;
-    }
-    std::lock_guard<std::mutex> lk(g_pin_mu);
-    g_pin_free.emplace_back(bytes, p);
-}
-
-void alloc_consumers(Shared* sh) {
-    const sdr_multi_opts& o = sh->o;
-    AudioRes& a = sh->ar;
-    const size_t lr_bytes = 2 * (size_t)sh->info.n_audio * o.nch * sizeof(int16_t);
-    a.pre = new_event();
-    a.pll = new_event();
-    a.post = new_event();
-    for (int k = 0; k < 2; k++) check_hip(hipMalloc(reinterpret_cast<void**>(&a.d_lr[k]), lr_bytes), "hipMalloc");
-    for (int h = 0; h < NH; h++) {
-        a.out_ready[h] = new_event();
-        a.d0[h] = timing_event();
-        a.d1[h] = timing_event();
-        pinned_get(&a.h_lr[h], lr_bytes);
-    }
-    RdsRes& r = sh->rr;
-    r.pre = new_event();
-    r.pll = new_event();
-    check_hip(hipMalloc(reinterpret_cast<void**>(&r.d_nbits), o.nch * sizeof(int32_t)), "hipMalloc");
-    check_hip(hipMalloc(reinterpret_cast<void**>(&r.d_bits), (size_t)o.nch * SDR_MAX_BITS), "hipMalloc");
-    for (int h = 0; h < NH; h++) {
-        r.out_ready[h] = new_event();
-        pinned_get(&r.h_nbits[h], o.nch * sizeof(int32_t));
-        pinned_get(&r.h_bits[h], (size_t)o.nch * SDR_MAX_BITS);
-    }
-}
-
-void free_consumers(Shared* sh) {
-    const sdr_multi_opts& o = sh->o;
-    AudioRes& a = sh->ar;
-    const size_t lr_bytes = 2 * (size_t)sh->info.n_audio * o.nch * sizeof(int16_t);
-    for (hipEvent_t e : {a.pre, a.pll, a.post}) (void)hipEventDestroy(e);
-    for (int h = 0; h < NH; h++) {
-        for (hipEvent_t e : {a.out_ready[h], a.d0[h], a.d1[h]}) (void)hipEventDestroy(e);
-        pinned_put(a.h_lr[h], lr_bytes);
-    }
-    for (int k = 0; k < 2; k++) (void)hipFree(a.d_lr[k]);
-    RdsRes& r = sh->rr;
-    for (hipEvent_t e : {r.pre, r.pll}) (void)hipEventDestroy(e);
-    (void)hipFree(r.d_nbits);
-    (void)hipFree(r.d_bits);
-    for (int h = 0; h < NH; h++) {
-        (void)hipEventDestroy(r.out_ready[h]);
-        pinned_put(r.h_nbits[h], o.nch * sizeof(int32_t));
-        pinned_put(r.h_bits[h], (size_t)o.nch * SDR_MAX_BITS);
+    consumer_loop(sh, ctx, 1, enqueue, frame_layer);
+    if (!o.out_prefix) return;
+    File f;
+    f.open(std::string(o.out_prefix) + ".rds", "w");
+    for (int c = 0; c < o.nch; c++) {
+        std::istringstream lines(fs[(size_t)c].text);
+        for (std::string line; std::getline(lines, line);) std::fprintf(f, "ch %d: %s\n", c, line.c_str());
     }
 }
 
@@ -864,77 +932,32 @@ long long regular_file_blocks(const char* path, size_t block_bytes) {
     return (long long)((size_t)sb.st_size / block_bytes);
 }
 
-// the tuning's bounds (sdr_tuner_set's), checked before anything starts
-bool tuning_valid(const sdr_multi_opts* o, const sdr_multi_tuning* t) {
-    int N = 0;
-    if (sdr_tuner_table(o->mode, nullptr, 0, &N) != SDR_OK) return false;
-    if (t->nsrc < 1 || t->nsrc > o->nch || !t->src || !t->khz) return false;
-    for (int c = 0; c < o->nch; c++)
-        if (t->src[c] < 0 || t->src[c] >= t->nsrc || 2 * (long long)t->khz[c] <= -(long long)N ||
-            2 * (long long)t->khz[c] > N)
-            return false;
-    return true;
-}
-
-int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo, const sdr_audio_opts* ao,
-              bool blend, sdr_multi_stats* stats, const sdr_multi_wide* wide = nullptr) {
-    if (!opts || opts->nch <= 0 || (!opts->in_path && (!opts->d_iq || opts->nblocks <= 0)))
-        return SDR_E_INVALID;
-    if (tune && !tuning_valid(opts, tune)) return SDR_E_INVALID;
-    int wide_R = 0, wide_iq = 0;
-    if (wide) {   // a wide run is always tuned, on rows the splitter makes
-        if (!tune || wide->nwide < 1 || wide->nwide > 4096 || wide->shift > 24 ||
-            sdr_split_geometry(opts->mode, wide->W, &wide_R, nullptr, &wide_iq, nullptr, nullptr) != SDR_OK ||
-            tune->nsrc > wide->nwide * wide_R)
-            return SDR_E_INVALID;
-        if (!opts->in_path && ((opts->row_stride & 3) || (reinterpret_cast<uintptr_t>(opts->d_iq) & 3) ||
-                               (opts->block_stride & 3) || opts->row_stride < 2 * (size_t)wide_iq))
-            return SDR_E_INVALID;
-    }
-    Shared sh;
-    sh.o = *opts;
-    sh.tuned = tune != nullptr;
-    sh.rows = wide ? wide->nwide : tune ? tune->nsrc : opts->nch;
+// a validated run, from its set-up to the last output; everything it made is released when it returns
+void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_stats* st) {
+    Shared sh(sw);
+    sh.o = *spec.o;
+    sh.tuned = spec.tune != nullptr;
+    sh.rows = spec.wide ? spec.wide->nwide : spec.tune ? spec.tune->nsrc : spec.o->nch;
     const sdr_multi_opts& o = sh.o;
-    check_hip(hipSetDevice(o.device), "hipSetDevice");
-    // SDR_MULTI_TRACE=1: the set-up and tear-down phases' host times on stderr
-    const bool trace = std::getenv("SDR_MULTI_TRACE") && std::atoi(std::getenv("SDR_MULTI_TRACE")) != 0;
-    const auto t_call = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (trace)
-            std::fprintf(stderr, "sdr_multi: %-16s %8.2f ms\n", what,
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
-    };
-    sh.ctx[0] = ctx_get(o.device, o.nch, o.mode, 0, o.flags);
-    sh.ctx[1] = ctx_get(o.device, o.nch, o.mode, 0, o.flags);
-    sh.ctx[2] = ctx_get(o.device, o.nch, o.mode, 1, o.flags);
+    for (int i = 0; i < 3; i++) sh.ctx[i].take(o.device, o.nch, o.mode, i == 2, o.flags, sw.ctx_cache);
     mark("contexts");
     // pooled contexts keep their tuning over sdr_ctx_reset: set it on every context of a tuned run,
     // clear it on those of an untuned one
     for (sdr_ctx* c : sh.ctx)
-        check_sdr(tune ? sdr_tuner_set(c, tune->nsrc, tune->src, tune->khz, nullptr) : sdr_tuner_set(c, 0, nullptr, nullptr, nullptr),
-                  "sdr_tuner_set");
+        check_sdr(spec.tune ? sdr_tuner_set(c, spec.tune->nsrc, spec.tune->src, spec.tune->khz, nullptr)
+                            : sdr_tuner_set(c, 0, nullptr, nullptr, nullptr), "sdr_tuner_set");
     check_sdr(sdr_ctx_info(sh.ctx[0], &sh.info), "sdr_ctx_info");
-    const size_t row = 2 * (size_t)sh.info.block_iq;
-    sh.in_row = wide ? 2 * (size_t)wide_iq : row;
-    if (!o.in_path && o.row_stride < sh.in_row) {
-        for (sdr_ctx* c : sh.ctx) ctx_put(c);
-        return SDR_E_INVALID;
-    }
-    if (wide) {
-        sh.split_rows = wide->nwide * wide_R;
-        check_sdr(sdr_split_create(&sh.split, o.device, o.mode, wide->W, wide->nwide, wide->shift), "sdr_split_create");
-    }
+    if (spec.wide) sh.split.emplace(o, *spec.wide);
+    sh.in_row = spec.wide ? 2 * (size_t)sh.split->wide_iq : 2 * (size_t)sh.info.block_iq;
     sh.nblocks_known = o.in_path ? regular_file_blocks(o.in_path, sh.in_row * (size_t)sh.rows) : o.nblocks;
     // streams: the PLLs on [0, pll_cus) (halves), everything else on the rest
     const int half = o.pll_cus / 2;
     if (half > 0) {
-        sh.s_fe = masked_stream(o.device, 0, o.pll_cus, 1);
-        sh.s_post = masked_stream(o.device, 0, o.pll_cus, 1);
-        if (const char* e = std::getenv("SDR_MULTI_POSTS"); e && std::atoi(e) == 2)
-            sh.s_post_c[1] = masked_stream(o.device, 0, o.pll_cus, 1);
-        sh.s_pll[0] = masked_stream(o.device, 0, half, 0);
-        sh.s_pll[1] = masked_stream(o.device, half, half, 0);
+        sh.s_fe.on_cus(o.device, 0, o.pll_cus, 1, sw.stream_cache);
+        sh.s_post.on_cus(o.device, 0, o.pll_cus, 1, sw.stream_cache);
+        if (sw.posts2) sh.s_post2.on_cus(o.device, 0, o.pll_cus, 1, sw.stream_cache);
+        sh.s_pll[0].on_cus(o.device, 0, half, 0, sw.stream_cache);
+        sh.s_pll[1].on_cus(o.device, half, half, 0, sw.stream_cache);
         sh.persistent = sh.nblocks_known > 0;
         for (int i = 0; i < 2 && sh.persistent; i++) {   // the library's residency rule (sdr_plls_fits)
             int waves = 0;
@@ -943,76 +966,30 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
                                     &groups, &resident), "sdr_plls_fits");
             sh.persistent = groups <= resident;
         }
-        if (sh.persistent) {   // the fill and drain stream (SDR_MULTI_EDGES=0: none)
-            const char* ed = std::getenv("SDR_MULTI_EDGES");
-            if (!ed || std::atoi(ed) != 0) {
-                hipDeviceProp_t prop;
-                check_hip(hipGetDeviceProperties(&prop, o.device), "hipGetDeviceProperties");
-                sh.s_all = masked_stream(o.device, 0, prop.multiProcessorCount, 0);
-                for (int i = 0; i < 3; i++) {
-                    sh.ev_first[i] = new_event();
-                    sh.ev_last[i] = new_event();
-                }
+        if (sh.persistent && sw.edges) {   // the fill and drain stream
+            hipDeviceProp_t prop;
+            check_hip(hipGetDeviceProperties(&prop, o.device), "hipGetDeviceProperties");
+            sh.s_all.on_cus(o.device, 0, prop.multiProcessorCount, 0, sw.stream_cache);
+            for (int i = 0; i < 3; i++) {
+                sh.ev_first[i].make();
+                sh.ev_last[i].make();
             }
         }
     } else {
-        sh.s_fe = plain_stream();
-        sh.s_post = plain_stream();
-        sh.s_pll[0] = plain_stream();
-        sh.s_pll[1] = plain_stream();
+        for (Stream* s : {&sh.s_fe, &sh.s_post, &sh.s_pll[0], &sh.s_pll[1]}) s->plain();
     }
     sh.s_post_c[0] = sh.s_post;
-    if (!sh.s_post_c[1]) sh.s_post_c[1] = sh.s_post;
-    if (o.in_path) sh.s_copy = plain_stream();
-    // SDR_MULTI_D2H=copy: the L/R copies on a stream of their own instead of after the post stages
-    if (const char* e = std::getenv("SDR_MULTI_D2H"); e && std::strcmp(e, "copy") == 0) sh.s_d2h = plain_stream();
+    sh.s_post_c[1] = sh.s_post2.s ? sh.s_post2.s : sh.s_post.s;
+    if (o.in_path) sh.s_copy.plain();
     mark("streams");
-    alloc_consumers(&sh);
-    MeterOut meter;
-    if (mo) {
-        meter.mo = *mo;
-        meter.nch = o.nch;
-        meter.mode = o.mode;
-        meter.sum.resize((size_t)o.nch);
-        check_sdr(sdr_meter_create(&meter.m, o.device, o.nch, o.mode), "sdr_meter_create");
-        for (auto& per : meter.h_rows)
-            for (uint8_t*& p : per) pinned_get(&p, (size_t)o.nch * sizeof(sdr_meter_row));
-        if (o.out_prefix) {
-            meter.f = std::fopen((std::string(o.out_prefix) + ".meter").c_str(), "wb");
-            if (!meter.f) die(std::string("cannot write ") + o.out_prefix + ".meter");
-        }
-        sh.meter = &meter;
-    }
-    AudioFin fin;
-    const size_t fin_bytes = 2 * (size_t)sh.info.n_audio * o.nch * sizeof(int16_t);
-    if (ao) {
-        fin.blend = blend;
-        check_sdr(sdr_audio_create(&fin.a, o.device, o.nch, o.mode, 2, ao), "sdr_audio_create");
-        check_sdr(sdr_audio_reset(fin.a, nullptr), "sdr_audio_reset");   // (synchronised with the batches below)
-        for (auto& p : fin.d_out) check_hip(hipMalloc(reinterpret_cast<void**>(&p), fin_bytes), "hipMalloc");
-        for (auto& p : fin.h_out) pinned_get(&p, fin_bytes);
-        if (o.out_prefix) {
-            fin.f = std::fopen((std::string(o.out_prefix) + ".audio").c_str(), "wb");
-            if (!fin.f) die(std::string("cannot write ") + o.out_prefix + ".audio");
-        }
-        sh.fin = &fin;
-    }
+    const size_t lr_bytes = 2 * (size_t)sh.info.n_audio * o.nch * sizeof(int16_t);
+    sh.ar.emplace(lr_bytes, sw.pin_cache);
+    sh.rr.emplace(o.nch, sw.pin_cache);
+    if (spec.meter) sh.meter.emplace(o, *spec.meter, sw.pin_cache);
+    if (spec.audio) sh.fin.emplace(o, *spec.audio, spec.blend, lr_bytes, sw.pin_cache);
     mark("consumer buffers");
-    // two recycled device batches of fm_demod [nch][block_if] (threadsafequeue.h's one slot, plus the
-    // one the producer fills meanwhile)
-    std::vector<FmBatch> batches(2);
-    for (auto& fb : batches) {
-        fb.nch = o.nch;
-        fb.n = sh.info.block_if;
-        fb.stride = (size_t)(fb.n + 63) / 64 * 64;
-        check_hip(hipMalloc(reinterpret_cast<void**>(&fb.d_fm), fb.stride * o.nch * sizeof(float)), "hipMalloc");
-        fb.ready = new_event();
-        for (auto& e : fb.released) {
-            e = new_event();
-            check_hip(hipEventRecord(e, nullptr), "hipEventRecord");   // trivially complete
-        }
-        sh.q.add_free(&fb);
-    }
+    // two recycled device batches (threadsafequeue.h's one slot, plus the one the producer fills meanwhile)
+    for (int i = 0; i < 2; i++) sh.q.add_free(&sh.batches.emplace_back(o.nch, sh.info.block_if).fb);
     check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize");
     mark("batches");
     // one persistent launch per consumer for every block (before the first sdr_push_fm_demod)
@@ -1020,8 +997,6 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
         check_sdr(sdr_plls_launch_sel(sh.ctx[1], (int)sh.nblocks_known, SDR_PLLS_STEREO, sh.s_pll[0]), "sdr_plls_launch_sel");
         check_sdr(sdr_plls_launch_sel(sh.ctx[2], (int)sh.nblocks_known, SDR_PLLS_RDS, sh.s_pll[1]), "sdr_plls_launch_sel");
     }
-    if (const char* e = std::getenv("SDR_MULTI_SYNC"); e && std::strcmp(e, "event") == 0) g_poll_events = false;
-    if (const char* e = std::getenv("SDR_MULTI_FILL"); e && std::atoi(e) == 0) sh.fill_gate = false;
     std::thread t_rds(rds_thread, &sh);      // project.cpp:134-136
     std::thread t_audio(audio_thread, &sh);
     std::thread t_rf(rf_thread, &sh);
@@ -1039,60 +1014,37 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
     t_rds.join();
     const auto t_end = std::chrono::steady_clock::now();
     mark("run end");
-    sdr_multi_stats st{};
-    st.blocks = sh.blocks;
-    st.seconds = std::chrono::duration<double>(t_end - t0).count();
-    st.steady_seconds = sh.blocks >= 2 ? std::chrono::duration<double>(t_end - sh.t_block1).count() : 0.0;
-    st.read_s = sh.read_s;
-    st.h2d_ms = sh.h2d_ms;
-    st.d2h_ms = sh.d2h_ms;
-    st.persistent = sh.persistent ? 1 : 0;
+    st->blocks = sh.blocks;
+    st->seconds = std::chrono::duration<double>(t_end - t0).count();
+    st->steady_seconds = sh.blocks >= 2 ? std::chrono::duration<double>(t_end - sh.t_block1).count() : 0.0;
+    st->read_s = sh.read_s;
+    st->h2d_ms = sh.h2d_ms;
+    st->d2h_ms = sh.d2h_ms;
+    st->persistent = sh.persistent ? 1 : 0;
     if (sh.persistent) {
         if (sh.blocks != sh.nblocks_known) die("sdr_multi: fewer blocks than the persistent launches cover");
         for (int i = 0; i < 2; i++) {
             double ms[1] = {0.0};
             int nb = 0;
             check_sdr(sdr_plls_report(sh.ctx[1 + i], ms, 0, &nb, sh.s_pll[i]), "sdr_plls_report");   // a timeout fails here
-            launch_period_ms(sh.ctx[1 + i], sh.s_pll[i], &st.pll_period_ms, &st.pll_span_ms,
-                             o.pll_end ? o.pll_end + (size_t)i * o.stamp_blocks : nullptr, o.stamp_blocks, trace);
+            launch_period_ms(sh.ctx[1 + i], sh.s_pll[i], &st->pll_period_ms, &st->pll_span_ms,
+                             o.pll_end ? o.pll_end + (size_t)i * o.stamp_blocks : nullptr, o.stamp_blocks, sw.trace);
         }
     }
+    // The one order that matters at the end: the device is idle before sh releases anything, and the
+    // splitter's clip counters are read while the splitter exists.
     check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    if (sh.split) {
-        if (wide->clips) check_sdr(sdr_split_clips(sh.split, wide->clips, nullptr), "sdr_split_clips");
-        check_sdr(sdr_split_destroy(sh.split), "sdr_split_destroy");
-    }
-    for (auto& fb : batches) {
-        (void)hipFree(fb.d_fm);
-        (void)hipEventDestroy(fb.ready);
-        for (auto& e : fb.released) (void)hipEventDestroy(e);
-    }
-    free_consumers(&sh);
-    if (mo) {
-        if (meter.f) std::fclose(meter.f);
-        if (o.out_prefix) meter.write_status(std::string(o.out_prefix) + ".status");
-        for (auto& per : meter.h_rows)
-            for (uint8_t* p : per) pinned_put(p, (size_t)o.nch * sizeof(sdr_meter_row));
-        check_sdr(sdr_meter_destroy(meter.m), "sdr_meter_destroy");
-    }
-    if (ao) {
-        if (fin.f) std::fclose(fin.f);
-        for (auto& p : fin.h_out) pinned_put(p, fin_bytes);
-        for (auto& p : fin.d_out) (void)hipFree(p);
-        check_sdr(sdr_audio_destroy(fin.a), "sdr_audio_destroy");
-    }
-    for (sdr_ctx* c : sh.ctx) ctx_put(c);
-    if (sh.s_d2h) (void)hipStreamDestroy(sh.s_d2h);
-    if (sh.s_post_c[1] != sh.s_post) release_masked(sh.s_post_c[1]);
-    if (sh.s_all) release_masked(sh.s_all);
-    for (int i = 0; i < 3; i++)
-        for (hipEvent_t ev : {sh.ev_first[i], sh.ev_last[i]})
-            if (ev) (void)hipEventDestroy(ev);
-    for (hipStream_t s : {sh.s_fe, sh.s_post, sh.s_pll[0], sh.s_pll[1]}) {
-        if (half > 0) release_masked(s);
-        else (void)hipStreamDestroy(s);
-    }
-    if (sh.s_copy) (void)hipStreamDestroy(sh.s_copy);
+    if (sh.split && spec.wide->clips) check_sdr(sdr_split_clips(sh.split->s, spec.wide->clips, nullptr), "sdr_split_clips");
+    if (sh.meter && o.out_prefix) sh.meter->write_status(std::string(o.out_prefix) + ".status");
+}
+
+int multi_run(const RunSpec& spec, sdr_multi_stats* stats) {
+    if (!validate(spec)) return SDR_E_INVALID;
+    check_hip(hipSetDevice(spec.o->device), "hipSetDevice");
+    const Switches sw{};
+    const Trace mark{sw.trace};
+    sdr_multi_stats st{};
+    run(spec, sw, mark, &st);
     mark("torn down");
     if (stats) *stats = st;
     return SDR_OK;
@@ -1101,34 +1053,28 @@ int multi_run(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sd
 }  // namespace
 
 extern "C" int sdr_multi_run(const sdr_multi_opts* opts, sdr_multi_stats* stats) {
-    return multi_run(opts, nullptr, nullptr, nullptr, false, stats);
+    return multi_run({opts}, stats);
 }
 
 extern "C" int sdr_multi_run_tuned(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, sdr_multi_stats* stats) {
-    return multi_run(opts, tune, nullptr, nullptr, false, stats);
+    return multi_run({opts, tune}, stats);
 }
 
 extern "C" int sdr_multi_run_metered(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo,
                                      sdr_multi_stats* stats) {
     if (!mo) return SDR_E_INVALID;
-    return multi_run(opts, tune, mo, nullptr, false, stats);
+    return multi_run({opts, tune, mo}, stats);
 }
 
 extern "C" int sdr_multi_run_finished(const sdr_multi_opts* opts, const sdr_multi_tuning* tune, const sdr_meter_opts* mo,
                                       const sdr_audio_opts* ao, int blend, sdr_multi_stats* stats) {
-    if (!opts || !ao || (blend && !mo)) return SDR_E_INVALID;
-    float a = 0.0f, b = 0.0f;   // what sdr_audio_create would refuse, before anything starts
-    if (sdr_audio_coeffs(opts->mode, ao->tau_us, &a, &b) != SDR_OK || !(ao->blend_hi > ao->blend_lo)) return SDR_E_INVALID;
-    return multi_run(opts, tune, mo, ao, blend != 0, stats);
+    if (!ao) return SDR_E_INVALID;
+    return multi_run({opts, tune, mo, ao, blend != 0}, stats);
 }
 
 extern "C" int sdr_multi_run_wide(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
                                   const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, sdr_multi_stats* stats) {
     if (!wide) return sdr_multi_run_finished(opts, tune, mo, ao, blend, stats);
-    if (!opts || !tune || (blend && (!mo || !ao))) return SDR_E_INVALID;
-    if (ao) {   // what sdr_audio_create would refuse, before anything starts (as sdr_multi_run_finished)
-        float a = 0.0f, b = 0.0f;
-        if (sdr_audio_coeffs(opts->mode, ao->tau_us, &a, &b) != SDR_OK || !(ao->blend_hi > ao->blend_lo)) return SDR_E_INVALID;
-    }
-    return multi_run(opts, tune, mo, ao, blend != 0, stats, wide);
+    if (!tune) return SDR_E_INVALID;
+    return multi_run({opts, tune, mo, ao, blend != 0, wide}, stats);
 }

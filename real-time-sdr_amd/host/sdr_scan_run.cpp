@@ -1,16 +1,22 @@
-// sdr_scan_run.cpp -- the band scan over a capture file (include/sdr_scan_run.h): read blocks of
-// capture rows, sdr_scan_block each, pick every row's stations, write the --tune list.
+// sdr_scan_run.cpp -- the band scans over a capture file, one loop for both: read blocks, sdr_scan_block
+// each, pick every row's stations, write the --tune list.
+//   sdr_scan_run (include/sdr_scan_run.h): the blocks hold capture rows; list entry src is the row.
+//   sdr_wide_scan_run (include/sdr_wide_scan.h): the blocks hold wide streams, which sdr_split_block cuts
+//     into capture rows in front of the scanner; every row is picked on the absolute station grid.
+// The plain scan is the wide one without a splitter: one row per input stream, the caller's pick options.
 #include "sdr_scan_run.h"
+#include "sdr_wide_scan.h"
 
 #include <hip/hip_runtime_api.h>
 
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <set>
 #include <vector>
 
 namespace {
-int fail(sdr_scan_run_stats* st, int code, const char* fmt, ...) {
+int fail(sdr_wide_scan_stats* st, int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     std::vsnprintf(st->error, sizeof(st->error), fmt, ap);
@@ -22,26 +28,36 @@ int fail(sdr_scan_run_stats* st, int code, const char* fmt, ...) {
 struct Run {
     FILE* in = nullptr;
     bool close_in = false;
+    sdr_split* split = nullptr;
     sdr_scan* scan = nullptr;
-    uint8_t* d_iq = nullptr;
+    uint8_t *d_in = nullptr, *d_rows = nullptr;   // the uploaded block; a wide scan's capture rows
     hipStream_t stream = nullptr;
     ~Run() {
         if (scan) sdr_scan_destroy(scan);
-        if (d_iq) (void)hipFree(d_iq);
+        if (split) sdr_split_destroy(split);
+        if (d_in) (void)hipFree(d_in);
+        if (d_rows) (void)hipFree(d_rows);
         if (stream) (void)hipStreamDestroy(stream);
         if (in && close_in) std::fclose(in);
     }
 };
-}  // namespace
 
-extern "C" int sdr_scan_run(const sdr_scan_run_opts* o, sdr_scan_run_stats* st) {
-    if (!st) return SDR_E_INVALID;
+// o->nwide input streams per block; wide: each is a wide stream of o->W, else a capture row (W, shift unused)
+int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st) {
+    const char* who = wide ? "wide scan" : "scan";
     std::memset(st, 0, sizeof(*st));
-    if (!o || !o->in_path || o->nrows < 1) return fail(st, SDR_E_INVALID, "scan: needs an input and nrows >= 1");
-    if (o->max_stations > 0 && (!o->src || !o->khz)) return fail(st, SDR_E_INVALID, "scan: null station arrays");
-    int N = 0, seg = 0, block_iq = 0;
-    if (sdr_scan_geometry(o->mode, &N, &seg, &block_iq) != SDR_OK) return fail(st, SDR_E_INVALID, "scan: %s", sdr_last_error());
+    if (!o || !o->in_path || o->nwide < 1)
+        return fail(st, SDR_E_INVALID, "%s: needs an input and %s >= 1", who, wide ? "nwide" : "nrows");
+    if (o->max_stations > 0 && (!o->src || !o->khz)) return fail(st, SDR_E_INVALID, "%s: null station arrays", who);
+    // (the plain scan leaves the step to sdr_scan_pick, after the blocks)
+    if (wide && o->pick.step_khz < 1) return fail(st, SDR_E_INVALID, "%s: step < 1", who);
+    int R = 1, in_iq = 0, half = 0, N = 0, block_iq = 0;
+    if ((wide && sdr_split_geometry(o->mode, o->W, &R, nullptr, &in_iq, &half, nullptr) != SDR_OK) ||
+        sdr_scan_geometry(o->mode, &N, nullptr, &block_iq) != SDR_OK)
+        return fail(st, SDR_E_INVALID, "%s: %s", who, sdr_last_error());
+    if (!wide) in_iq = block_iq;
     const int max_blocks = o->max_blocks > 0 ? o->max_blocks : 4;
+    const int nrows = o->nwide * R;
     Run r;
     if (std::strcmp(o->in_path, "-") == 0) {
         r.in = stdin;
@@ -49,37 +65,62 @@ extern "C" int sdr_scan_run(const sdr_scan_run_opts* o, sdr_scan_run_stats* st) 
         r.in = std::fopen(o->in_path, "rb");
         r.close_in = true;
     }
-    if (!r.in) return fail(st, SDR_E_INVALID, "scan: cannot open %s", o->in_path);
-    const size_t row_bytes = (size_t)2 * block_iq, block_bytes = row_bytes * (size_t)o->nrows;
-    int rc = sdr_scan_create(&r.scan, o->device, o->mode, o->nrows);
-    if (rc != SDR_OK) return fail(st, rc, "scan: %s", sdr_last_error());
-    if (hipSetDevice(o->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&r.d_iq), block_bytes) != hipSuccess ||
-        hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking) != hipSuccess)
+    if (!r.in) return fail(st, SDR_E_INVALID, "%s: cannot open %s", who, o->in_path);
+    const size_t in_bytes = (size_t)2 * in_iq, block_bytes = in_bytes * (size_t)o->nwide;
+    const size_t row_bytes = (size_t)2 * block_iq;
+    int rc = wide ? sdr_split_create(&r.split, o->device, o->mode, o->W, o->nwide, o->shift) : SDR_OK;
+    if (rc == SDR_OK) rc = sdr_scan_create(&r.scan, o->device, o->mode, nrows);
+    if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
+    if (hipSetDevice(o->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&r.d_in), block_bytes) != hipSuccess ||
+        (wide && hipMalloc(reinterpret_cast<void**>(&r.d_rows), row_bytes * (size_t)nrows) != hipSuccess) ||
+        hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking) != hipSuccess) {
+        if (wide)
+            return fail(st, SDR_E_HIP, "wide scan: no device buffers of %zu and %zu bytes or no stream", block_bytes,
+                        row_bytes * (size_t)nrows);
         return fail(st, SDR_E_HIP, "scan: no device buffer of %zu bytes or no stream", block_bytes);
+    }
     std::vector<uint8_t> host(block_bytes);
     while (st->blocks < max_blocks && std::fread(host.data(), 1, block_bytes, r.in) == block_bytes) {
-        // (the copy returns once the pageable buffer is staged; the kernels of the previous block
-        // read d_iq in stream order before it)
-        if (hipMemcpyAsync(r.d_iq, host.data(), block_bytes, hipMemcpyHostToDevice, r.stream) != hipSuccess ||
+        // (the copy returns once the pageable buffer is staged; the kernels of the previous block read
+        // d_in and d_rows in stream order before it)
+        if (hipMemcpyAsync(r.d_in, host.data(), block_bytes, hipMemcpyHostToDevice, r.stream) != hipSuccess ||
             hipStreamSynchronize(r.stream) != hipSuccess)
-            return fail(st, SDR_E_HIP, "scan: upload of block %lld failed", st->blocks);
-        rc = sdr_scan_block(r.scan, r.d_iq, row_bytes, r.stream);
-        if (rc != SDR_OK) return fail(st, rc, "scan: %s", sdr_last_error());
+            return fail(st, SDR_E_HIP, "%s: upload of block %lld failed", who, st->blocks);
+        if (wide) rc = sdr_split_block(r.split, reinterpret_cast<const int8_t*>(r.d_in), in_bytes, r.d_rows, row_bytes, r.stream);
+        if (rc == SDR_OK) rc = sdr_scan_block(r.scan, wide ? r.d_rows : r.d_in, row_bytes, r.stream);
+        if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
         st->blocks++;
     }
-    if (st->blocks == 0) return fail(st, SDR_E_INVALID, "scan: %s holds no whole block of %d rows (%zu bytes)", o->in_path, o->nrows, block_bytes);
-    std::vector<float> psd((size_t)o->nrows * N);
+    if (st->blocks == 0)
+        return fail(st, SDR_E_INVALID, "%s: %s holds no whole block of %d %s (%zu bytes)", who, o->in_path, o->nwide,
+                    wide ? "wide streams" : "rows", block_bytes);
+    std::vector<float> psd((size_t)nrows * N);
     rc = sdr_scan_psd(r.scan, psd.data(), &st->segments, r.stream);
-    if (rc != SDR_OK) return fail(st, rc, "scan: %s", sdr_last_error());
+    std::vector<long long> clips((size_t)nrows);
+    if (rc == SDR_OK && wide) rc = sdr_split_clips(r.split, clips.data(), r.stream);
+    if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
+    for (long long c : clips) st->clips += c;
     std::vector<int32_t> src, khz, row_khz(N + 1);
     std::vector<float> row_db(N + 1);
-    for (int row = 0; row < o->nrows; row++) {
-        int n = 0;
-        rc = sdr_scan_pick(o->mode, psd.data() + (size_t)row * N, &o->pick, row_khz.data(), row_db.data(), N + 1, &n);
-        if (rc != SDR_OK) return fail(st, rc, "scan: %s", sdr_last_error());
-        for (int i = 0; i < n && i <= N; i++) {
-            src.push_back(row);
-            khz.push_back(row_khz[i]);
+    const long long step = o->pick.step_khz;
+    for (int w = 0; w < o->nwide; w++) {
+        std::set<long long> seen;                      // absolute kHz already given by an earlier row of this wide stream
+        for (int row = 0; row < R; row++) {
+            sdr_scan_opts p = o->pick;
+            long long centre = 0;
+            if (wide) {
+                centre = (long long)(row - (o->W - 1)) * half;
+                p.guard_khz = N / 4;
+                p.first_khz = (int)((((long long)o->pick.first_khz - centre) % step + step) % step);
+            }
+            int n = 0;
+            rc = sdr_scan_pick(o->mode, psd.data() + ((size_t)w * R + row) * N, &p, row_khz.data(), row_db.data(), N + 1, &n);
+            if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
+            for (int i = 0; i < n && i <= N; i++)
+                if (!wide || seen.insert(centre + row_khz[i]).second) {
+                    src.push_back(w * R + row);
+                    khz.push_back(row_khz[i]);
+                }
         }
     }
     st->stations = (int)src.size();
@@ -89,9 +130,38 @@ extern "C" int sdr_scan_run(const sdr_scan_run_opts* o, sdr_scan_run_stats* st) 
     }
     if (o->out_path) {
         FILE* f = std::fopen(o->out_path, "w");
-        if (!f) return fail(st, SDR_E_INVALID, "scan: cannot write %s", o->out_path);
+        if (!f) return fail(st, SDR_E_INVALID, "%s: cannot write %s", who, o->out_path);
         for (size_t i = 0; i < src.size(); i++) std::fprintf(f, "%d %d\n", (int)src[i], (int)khz[i]);
-        if (std::fclose(f) != 0) return fail(st, SDR_E_INVALID, "scan: cannot write %s", o->out_path);
+        if (std::fclose(f) != 0) return fail(st, SDR_E_INVALID, "%s: cannot write %s", who, o->out_path);
     }
     return SDR_OK;
+}
+}  // namespace
+
+extern "C" int sdr_wide_scan_run(const sdr_wide_scan_opts* o, sdr_wide_scan_stats* st) {
+    return st ? scan_file(o, true, st) : SDR_E_INVALID;
+}
+
+extern "C" int sdr_scan_run(const sdr_scan_run_opts* o, sdr_scan_run_stats* st) {
+    if (!st) return SDR_E_INVALID;
+    sdr_wide_scan_opts w{};
+    if (o) {
+        w.nwide = o->nrows;
+        w.mode = o->mode;
+        w.device = o->device;
+        w.in_path = o->in_path;
+        w.out_path = o->out_path;
+        w.max_blocks = o->max_blocks;
+        w.pick = o->pick;
+        w.max_stations = o->max_stations;
+        w.src = o->src;
+        w.khz = o->khz;
+    }
+    sdr_wide_scan_stats ws;
+    const int rc = scan_file(o ? &w : nullptr, false, &ws);
+    st->stations = ws.stations;
+    st->blocks = ws.blocks;
+    st->segments = ws.segments;
+    std::memcpy(st->error, ws.error, sizeof(st->error));
+    return rc;
 }

@@ -2,7 +2,7 @@
 # bench's device-generated input, at BLOCKS block counts, REPS interleaved rounds, once per setting in
 # ENVS (space-separated NAME=value[,NAME=value] items; "-" = none), e.g. the engine's A/B knobs
 # SDR_MULTI_EDGES (0: no all-CU fill/drain stream), SDR_MULTI_POSTS (2: a post stream per consumer),
-# SDR_MULTI_D2H (copy: L/R copies on their own stream), SDR_MULTI_SYNC (event: hipEventSynchronize).
+# SDR_MULTI_FILL (0: block 1's front end beside block 0's pre parts); sdr_multi_engine.cpp lists them all.
 #   TAG=... [BLOCKS="25 60"] [ENVS="- SDR_MULTI_EDGES=0"] [REPS=2] bash tools/gpu/queue_ab.sh
 set -o pipefail
 export TMPDIR=/tmp
