@@ -7,12 +7,17 @@ per step), builds the VGPR def-use graph of the chunk (64-bit operands as regist
 op_sel sources included) and reports:
   * VALU / SALU / LDS / s_nop per step, and f64 operations per step by kind;
   * the longest dependence chain through the chunk (the recurrence: 16 steps deep), per step;
-  * one step's listing with each instruction marked [f64] and [chain] (on a longest path).
-  python tools/pll_isa.py [--out profiles/r04/pll_step_isa.txt]
+  * one step's listing with each instruction marked [f64] and [chain] (on a longest path);
+  * the chunk block as a whole (up to the redo branch; the stores and refill loads follow the redo's
+    join): instructions per chunk by class, and the remainder that is left after 16 times the step's
+    share of each opcode (the chunk-level work: table reads, waits, the verdict, the redo branch), by
+    class and by opcode; the spill traffic inside the block; a digest of every copy of the chunk.
+  python tools/pll_isa.py [--out profiles/r04/pll_step_isa.txt] [--chunk-out chunk_block.txt]
 """
 from __future__ import annotations
 
 import argparse
+import hashlib
 import pathlib
 import re
 import subprocess
@@ -50,14 +55,39 @@ def parse(line: str):
     return op, ops, mods, s
 
 
+CLASSES = ("VALU", "SALU", "VMEM", "LDS", "s_waitcnt", "s_nop")
+
+
+def klass(op: str) -> str:
+    if op == "s_nop":
+        return "s_nop"
+    if op == "s_waitcnt":
+        return "s_waitcnt"
+    if op.startswith("v_"):
+        return "VALU"
+    if op.startswith("ds_"):
+        return "LDS"
+    if op.startswith(("global_", "buffer_", "scratch_", "flat_")):
+        return "VMEM"
+    return "SALU"
+
+
+def short(op: str) -> str:
+    """opcode without its encoding suffix (v_mov_b32_e32 and v_mov_b32_dpp stay apart)"""
+    return re.sub(r"_(e32|e64)$", "", op)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--extra", default="", help="extra compiler flags (scheduler A/B)")
+    ap.add_argument("--chunk-out", default=None, help="write the whole chunk block's listing here")
+    ap.add_argument("--src", default=str(ROOT / "real-time-sdr_amd/csrc/sdr_pll.hip"),
+                    help="the unit to compile (another revision's csrc/sdr_pll.hip, beside its own headers)")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as d:
         obj = pathlib.Path(d) / "pll.o"
-        subprocess.run([HIPCC, *FLAGS, *args.extra.split(), "-o", str(obj), str(ROOT / "real-time-sdr_amd/csrc/sdr_pll.hip")],
+        subprocess.run([HIPCC, *FLAGS, *args.extra.split(), "-o", str(obj), args.src],
                        check=True)
         dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", str(obj)], capture_output=True, text=True,
                              check=True).stdout
@@ -75,24 +105,19 @@ def main() -> None:
             blocks.append(cur)
             cur = []
     # (16 more bitop3 with the base-angle table of SDR_PLL_BASETAB)
-    chunk = next(b for b in blocks if sum(x[0] == "v_bitop3_b32" for x in b) in (16, 32)
-                 and sum(x[0] == "ds_read_b128" for x in b) >= 8)
+    chunks = [b for b in blocks if sum(x[0] == "v_bitop3_b32" for x in b) in (16, 32)
+              and sum(x[0] == "ds_read_b128" for x in b) >= 8]
+    chunk = chunks[0]
     steps = 16
     cnt = {"VALU": 0, "SALU": 0, "LDS": 0, "s_nop": 0, "VMEM": 0}
     f64 = {}
     for op, _, _, _ in chunk:
-        if op == "s_nop":
-            cnt["s_nop"] += 1
-        elif op.startswith("v_"):
-            cnt["VALU"] += 1
-            if F64.match(op):
-                f64[op] = f64.get(op, 0) + 1
-        elif op.startswith("s_"):
-            cnt["SALU"] += 1
-        elif op.startswith("ds_"):
-            cnt["LDS"] += 1
-        elif op.startswith(("global_", "buffer_")):
-            cnt["VMEM"] += 1
+        k = klass(op)
+        if k == "s_waitcnt":                              # per step it counts with the SALU, as before
+            k = "SALU"
+        cnt[k] += 1
+        if k == "VALU" and F64.match(op):
+            f64[op] = f64.get(op, 0) + 1
     # def-use graph (VALU only; the first operand is the destination of every VALU form used here)
     last_def: dict[str, int] = {}
     depth = [0] * len(chunk)
@@ -135,6 +160,39 @@ def main() -> None:
         op, _, _, text = chunk[i]
         mark = ("[f64]" if F64.match(op) else "     ") + (" [chain]" if i in chain else "        ")
         out.append(f"  {mark}  {text}")
+    # the chunk block as a whole, and what is left of it after 16 times the listed step
+    whole = {k: 0 for k in CLASSES}
+    ops_whole: dict[str, int] = {}
+    for op, _, _, _ in chunk:
+        whole[klass(op)] += 1
+        ops_whole[short(op)] = ops_whole.get(short(op), 0) + 1
+    # a step's share of an opcode is the nearest multiple of 16 (every step issues the same VALU, give or
+    # take an fma chosen as fmac); everything that is not VALU is chunk-level
+    ops_rest = {o: (v - steps * round(v / steps) if o.startswith("v_") else v) for o, v in ops_whole.items()}
+    rest = {k: 0 for k in CLASSES}
+    for o, v in ops_rest.items():
+        rest[klass(o)] += v
+    out.append("")
+    out.append(f"the chunk block: {len(chunk)} instructions = {len(chunk) / steps:.2f} per step")
+    out.append("  per chunk:      " + ", ".join(f"{k} {whole[k]}" for k in CLASSES))
+    out.append(f"  remainder (per opcode, what is left after 16 x the step's share): {sum(rest.values())} instructions: " +
+               ", ".join(f"{k} {rest[k]}" for k in CLASSES))
+    out.append("  spill traffic in the block: " +
+               ", ".join(f"{o} {ops_whole.get(o, 0)}" for o in ("v_readlane_b32", "v_writelane_b32", "v_accvgpr_read_b32",
+                                                               "v_accvgpr_write_b32", "scratch_load_dword", "scratch_store_dword")))
+    out.append("  remainder by opcode:")
+    for o, v in sorted(ops_rest.items(), key=lambda kv: (-kv[1], kv[0])):
+        if v:
+            out.append(f"    {v:4d}  {o}")
+    # every copy of the table chunk in the kernel (the gated fill block's loop and the plain loop, each
+    # unrolled over the register buffers, and the chunk past the loop): a digest of each listing, so that
+    # two builds can be compared copy by copy
+    out.append(f"  table-chunk blocks in the kernel: {len(chunks)}; instructions and sha1 of each listing:")
+    for b in chunks:
+        digest = hashlib.sha1("\n".join(x[3] for x in b).encode()).hexdigest()[:12]
+        out.append(f"    {len(b):4d}  {digest}")
+    if args.chunk_out:
+        pathlib.Path(args.chunk_out).write_text("\n".join(x[3] for x in chunk) + "\n")
     txt = "\n".join(out) + "\n"
     if args.out:
         pathlib.Path(args.out).write_text(txt)
