@@ -489,7 +489,17 @@ __device__ __forceinline__ void pair_chunk(PairChain& p, const float (&xb)[PLL_C
     const SplitRegs snap = p.r;
     PllProof pf;
 #pragma unroll
-    for (int j = 0; j < C; j++) pll_step_split<TAB>(p.r, xb[j], rb[j], p.w, TAB ? wv[j] : 0.0, tv[j], pf, L);
+    for (int j = 0; j < C; j++) {
+        // the table reads were issued two steps (~400 cycles) ago: one wait for the rest of them here,
+        // tied to the chain by the state word, instead of a counted s_waitcnt in front of each of steps
+        // 2..7 (8 -> 2 waits per chunk; profiles/r14/pll_phase_store/)
+        static_assert(C == 16, "the wait below names the table registers of a 16-step chunk");
+        if (TAB && j == 2)
+            asm("" : "+v"(p.r.s), "+v"(wv[2]), "+v"(wv[3]), "+v"(wv[4]), "+v"(wv[5]), "+v"(wv[6]), "+v"(wv[7]),
+                     "+v"(wv[8]), "+v"(wv[9]), "+v"(wv[10]), "+v"(wv[11]), "+v"(wv[12]), "+v"(wv[13]),
+                     "+v"(wv[14]), "+v"(wv[15]));
+        pll_step_split<TAB>(p.r, xb[j], rb[j], p.w, TAB ? wv[j] : 0.0, tv[j], pf, L);
+    }
     // this lane's proof: its half of the e bracket, the e range, its own rounding ties, and
     // the state range (a NaN from an invalid input fails it)
     const bool ok = (pf.emaxf < PLL_EMAX_F) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
@@ -579,11 +589,30 @@ __device__ __forceinline__ void pll_run_split(const PllJob& jb, int n, int ch, c
 #pragma unroll
         for (int u = 0; u < NB; u++) load_chunk(xb[u], rb[u], min(u, clast) * C);
     }
+    // VEC: both lanes of a pair hold the same 16 phases, and a store costs the lone wave per instruction,
+    // not per byte (two of the four stores removed: -2.1 cycles per step, profiles/r14/pll_phase_store/).
+    // So each lane stores one half, the even lane t[i0 .. i0+7], the odd lane t[i0+8 .. i0+15]: two
+    // 16-byte stores per chunk, their 8 dwords picked from tv by v_bfi_b32 against a per-lane mask in a
+    // VGPR (no branch, no exec change; written out, because the compiler makes v_and + v_and_or of the
+    // C form, and an SGPR-pair mask costs a lone wave more, profiles/HISTORY.md 4a round 4). A redone
+    // chunk leaves its phases in the same tv.
+    uint32_t half_mask = L.a ? 0u : ~0u;
+    asm("" : "+v"(half_mask));
+    float* const tbh = tb + (L.a ? 0 : C / 2);
     auto store_chunk = [&](const float (&tv)[C], int i0) {
         if (VEC) {
+            float h[C / 2];
 #pragma unroll
-            for (int k = 0; k < C / 4; k++)
-                reinterpret_cast<float4*>(tb + i0)[k] = make_float4(tv[4 * k], tv[4 * k + 1], tv[4 * k + 2], tv[4 * k + 3]);
+            for (int k = 0; k < C / 2; k++) {
+                uint32_t d;
+                asm("v_bfi_b32 %0, %1, %2, %3"
+                    : "=v"(d)
+                    : "v"(half_mask), "v"(__builtin_bit_cast(uint32_t, tv[k + C / 2])), "v"(__builtin_bit_cast(uint32_t, tv[k])));
+                h[k] = __builtin_bit_cast(float, d);
+            }
+#pragma unroll
+            for (int k = 0; k < C / 8; k++)
+                reinterpret_cast<float4*>(tbh + i0)[k] = make_float4(h[4 * k], h[4 * k + 1], h[4 * k + 2], h[4 * k + 3]);
         } else {
 #pragma unroll
             for (int k = 0; k < C; k++) tb[i0 + k] = tv[k];
