@@ -16,7 +16,7 @@ SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc
             $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip $(PKG)/csrc/sdr_split.hip \
             $(PKG)/csrc/sdr_taps.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
-HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h
+HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h $(PKG)/csrc/demod_phase.h
 
 # host C++ (no device code): compiled by the system g++ against the HIP runtime headers
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include \

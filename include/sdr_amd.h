@@ -48,6 +48,41 @@ extern "C" {
 #define SDR_FLAG_KEEP_INTERMEDIATES 0x4  /* post stages store every intermediate row (carrier, stereo_dc,
                                           * ipll) for sdr_ctx_buffer; by default the NCO, mixers and
                                           * resamplers are fused and only the rows' history is stored */
+#define SDR_FLAG_PHASE_DEMOD 0x8    /* phase discriminator (below): fm_demod is the phase step in radians,
+                                     * not its sine; not with SDR_FLAG_FAST_FRONTEND (SDR_E_INVALID) */
+
+/* ---- phase discriminator (no reference counterpart; sdr_version stays 3, callers detect it by symbol).
+ * fmDemodNoArctan's value is Im(x[n] conj(x[n-1])) / |x[n]|^2 = (|x[n-1]| / |x[n]|) sin(dphi): the sine of
+ * the phase step between two IF samples, which stops growing at a deviation of if_Fs / 4 (60, 90, 60,
+ * 96 kHz in modes 0-3) and folds beyond it. With SDR_FLAG_PHASE_DEMOD the front end's FIRs are unchanged
+ * and every fm_demod sample is the step itself, in radians, in [-RN32(pi), RN32(pi)]. All f32, every
+ * product, sum and quotient rounded on its own (no FMA), f32 subnormals kept; (Ip, Qp) is the previous
+ * FIR output, the block's first uses the carried one, (0, 0) after create / reset:
+ *     re = fl(fl(I Ip) + fl(Q Qp))        im = fl(fl(Q Ip) - fl(I Qp))
+ *     a = |re|, b = |im|, mx = max(a, b), mn = min(a, b)
+ *     mx == 0            -> +0       (the reference's I = Q = 0 rule, and a zero previous sample)
+ *     z = fl(mn / mx)    the correctly rounded quotient;  u = fl(z z)
+ *     p = c_K;  p = fl(fl(p u) + c_k) for k = K-1 .. 0;  r = fl(p z)
+ *     b > a  -> r = fl(RN32(pi/2) - r);   re < 0 -> r = fl(RN32(pi) - r);   out = copysign(r, im)
+ * K = 7: atan(z) ~ z (c_0 + c_1 z^2 + .. + c_7 z^14) on [0, 1], a minimax fit with c_0 = 1 held (so a
+ * small step is fl(z) times a factor within an ulp of 1) whose real-arithmetic error is 4.9e-8 rad.
+ * Against f64 atan2(im, re) of the same f32 (re, im) the f32 evaluation above is within 2^-20 rad
+ * (required, tests/test_demod_model.py); measured over every z = m 2^-24 in all eight octant and sign
+ * cases and 10^6 random pairs: 3.39e-7 rad = 0.355 x 2^-20. For small steps the value equals the sine
+ * discriminator's, so the audio, the PLL inputs and short(16384 y) keep their scale. */
+#define SDR_DEMOD_K 7
+#define SDR_DEMOD_C0 0x1p+0f
+#define SDR_DEMOD_C1 -0x1.5550f2p-2f
+#define SDR_DEMOD_C2 0x1.98d61p-3f
+#define SDR_DEMOD_C3 -0x1.1e3d8cp-3f
+#define SDR_DEMOD_C4 0x1.912bfep-4f
+#define SDR_DEMOD_C5 -0x1.d948p-5f
+#define SDR_DEMOD_C6 0x1.797d56p-6f
+#define SDR_DEMOD_C7 -0x1.1d6f96p-8f
+#define SDR_DEMOD_PI_2 0x1.921fb6p+0f   /* RN32(pi / 2) */
+#define SDR_DEMOD_PI 0x1.921fb6p+1f     /* RN32(pi) */
+/* host only, no GPU: *n = K + 1, c[0 .. K] filled when c != NULL and max >= K + 1 */
+int sdr_demod_coeffs(float *c, int max, int *n);
 
 /* pllblock_args, include/pll.h:10-17 (same field order and types) */
 typedef struct sdr_pll_state {
@@ -99,6 +134,10 @@ int sdr_convolve_fir_resample(float *y, size_t y_stride, const float *x, size_t 
 /* fmDemodNoArctan(I, Q, prevI, prevQ, out): demod.cpp:3-24 (include/demod.h:5). prev: [nch][2]. */
 int sdr_fm_demod(float *out, size_t out_stride, const float *I, const float *Q, size_t iq_stride, int nch,
                  int n, float *prev, void *stream);
+/* The phase discriminator (SDR_FLAG_PHASE_DEMOD above) on the same arguments: out is the phase step in
+ * radians; prev: [nch][2] = the last (I, Q), updated in place. */
+int sdr_fm_demod_phase(float *out, size_t out_stride, const float *I, const float *Q, size_t iq_stride, int nch,
+                       int n, float *prev, void *stream);
 /* fmpll(in, freq, Fs, out, state, ncoScale, phaseAdjust, bw): pll.cpp:4-61 (include/pll.h:20).
  * out: [nch][n+1]; out[ch][0] is set from state[ch].lastCarrier (the previous block's last
  * sample, pll.cpp:18), state[ch].lastCarrier <- out[ch][n]. */
@@ -328,6 +367,12 @@ typedef struct sdr_meter_state {
  * A ratio with a zero numerator (or eye_n = 0) is 0, one with a zero denominator under a positive
  * numerator is +infinity; the dB of 0 is -infinity. */
 int sdr_meter_status(int mode, const sdr_meter_row *row, const sdr_meter_opts *o, sdr_meter_state *out);
+/* One row's discriminator readings as FM deviation in kHz, in double (n = block_if, k = if_Fs / (2 pi 1000)):
+ *   peak_khz = k fm_peak,  rms_khz = k sqrt(fm_sq / n),  offset_khz = k fm_sum / n
+ * Meaningful only for rows of a context with SDR_FLAG_PHASE_DEMOD, whose fm_demod is the phase step in
+ * radians; on a default context's rows the same formula is the small-signal conversion the note above
+ * warns about. Host only, no GPU; any output pointer may be NULL. */
+int sdr_meter_deviation(int mode, const sdr_meter_row *row, double *peak_khz, double *rms_khz, double *offset_khz);
 /* device: the meter is its own handle, like the scanner; it owns the taps and rows[nch] (all zero after
  * create and sdr_meter_reset). Both calls enqueue one kernel on `stream` and write their fields of every
  * channel's row for `ctx`'s current block; they may use two contexts (an audio and an RDS one joined by

@@ -23,7 +23,8 @@ extern "C" {
 #endif
 
 typedef struct sdr_multi_opts {
-    int nch, mode, flags, device;
+    int nch, mode, flags, device;   /* flags: sdr_ctx_create's; SDR_FLAG_FAST_FRONTEND | SDR_FLAG_PHASE_DEMOD is
+                                     * SDR_E_INVALID, before anything is created */
     /* CUs [0, pll_cus) carry the two consumers' PLLs (stereo on the first half, RDS on the second,
      * one persistent launch each, sdr_plls_launch_sel) and every other stream runs on the rest;
      * 0: no CU masks and per-block PLL dispatches. A byte stream of unknown length (a pipe) also

@@ -12,7 +12,12 @@
  *                     ch <c>: offset <v> level_db <v> pilot_nr <v> rds_nr <v> eye_db <v> flags <F>
  *                   the run's means of sdr_meter_status's readings over its blocks (discriminator
  *                   units and ratios, not kHz of deviation) and, joined by '|', the flags STEREO, RDS,
- *                   OFFTUNE, DEAD_AIR that held on more than half the blocks ('-' when none did). */
+ *                   OFFTUNE, DEAD_AIR that held on more than half the blocks ('-' when none did).
+ *                   A run whose opts->flags hold SDR_FLAG_PHASE_DEMOD (the phase discriminator: the rows'
+ *                   fm fields are radians) ends every line with
+ *                     " peak_khz <v> offset_khz <v>"
+ *                   the run's maximum of sdr_meter_deviation's peak and the mean of its offset, in kHz
+ *                   of deviation; without that flag the file is byte for byte what it was. */
 #ifndef SDR_MULTI_METER_H
 #define SDR_MULTI_METER_H
 

@@ -32,6 +32,7 @@ SDR_NBITS_POISONED = -2      # nbits of such a block (its rds_clean rows are NaN
 FLAG_FAST_FRONTEND = 0x1
 FLAG_PLL_LIBM = 0x2
 FLAG_KEEP_INTERMEDIATES = 0x4
+PHASE_DEMOD = FLAG_PHASE_DEMOD = 0x8   # fm_demod is the phase step in radians (include/sdr_amd.h); not with FAST
 
 _lib = None
 
@@ -112,6 +113,9 @@ def lib() -> C.CDLL:
         "sdr_convolve_fir": ([vp, sz, vp, sz, i32, i32, vp, i32, vp, i32, i32, vp], i32),
         "sdr_convolve_fir_resample": ([vp, sz, vp, sz, i32, i32, vp, i32, vp, i32, i32, i32, vp], i32),
         "sdr_fm_demod": ([vp, sz, vp, vp, sz, i32, i32, vp, vp], i32),
+        "sdr_fm_demod_phase": ([vp, sz, vp, vp, sz, i32, i32, vp, vp], i32),
+        "sdr_demod_coeffs": ([vp, i32, C.POINTER(i32)], i32),
+        "sdr_meter_deviation": ([i32, C.POINTER(MeterRow)] + [C.POINTER(C.c_double)] * 3, i32),
         "sdr_fmpll": ([vp, sz, vp, sz, i32, i32, f32, f32, vp, f32, f32, f32, vp], i32),
         "sdr_cdr": ([vp, vp, sz, i32, i32, i32, vp], i32),
         "sdr_ctx_create": ([C.POINTER(vp), i32, i32, i32, i32, i32], i32),
@@ -498,6 +502,24 @@ def meter_status(mode: int, rows, **opts):
     return out.reshape(rows.shape)
 
 
+def meter_deviation(mode: int, rows):
+    """sdr_meter_deviation of every row (host only): a numpy structured array (peak_khz, rms_khz,
+    offset_khz) of the rows' shape. Deviation in kHz only for rows of a PHASE_DEMOD pipeline."""
+    import numpy as np
+    if isinstance(rows, MeterRow):
+        rows = np.frombuffer(bytes(rows), dtype=meter_row_dtype())[0]
+    rows = np.asarray(rows, dtype=meter_row_dtype())
+    flat = np.ascontiguousarray(rows).reshape(-1)
+    out = np.zeros(flat.shape, np.dtype([("peak_khz", "f8"), ("rms_khz", "f8"), ("offset_khz", "f8")]))
+    pk, rms, off = C.c_double(), C.c_double(), C.c_double()
+    for i in range(flat.size):
+        row = MeterRow.from_buffer_copy(flat[i].tobytes())
+        check(lib().sdr_meter_deviation(mode, C.byref(row), C.byref(pk), C.byref(rms), C.byref(off)),
+              "sdr_meter_deviation")
+        out[i] = (pk.value, rms.value, off.value)
+    return out.reshape(rows.shape)
+
+
 class Meter:
     """The reception meter of `nch` channels of one mode (sdr_meter_*): per block audio(pipe, lr) after
     the block's stereo stage and rds(pipe) after its RDS stage -- on one Pipeline or on two joined by
@@ -672,6 +694,26 @@ def fm_demod(out, I, Q, prev, stream=None):
     check(lib().sdr_fm_demod(_ptr(out), _row_stride(out), _ptr(I), _ptr(Q), _row_stride(I), nch, n, _ptr(prev),
                              _stream(stream)), "fm_demod")
     return out
+
+
+def fm_demod_phase(out, I, Q, prev, stream=None):
+    """The phase discriminator (PHASE_DEMOD, include/sdr_amd.h) for every row: the phase step in radians;
+    prev[nch][2] = (prev_I, prev_Q), updated in place."""
+    nch, n = I.shape
+    assert Q.stride(0) == I.stride(0)
+    check(lib().sdr_fm_demod_phase(_ptr(out), _row_stride(out), _ptr(I), _ptr(Q), _row_stride(I), nch, n, _ptr(prev),
+                                   _stream(stream)), "fm_demod_phase")
+    return out
+
+
+def demod_coeffs():
+    """c_0 .. c_K of the phase discriminator's odd polynomial (sdr_demod_coeffs, host only)."""
+    import numpy as np
+    n = C.c_int(0)
+    check(lib().sdr_demod_coeffs(None, 0, C.byref(n)), "sdr_demod_coeffs")
+    c = np.zeros(n.value, np.float32)
+    check(lib().sdr_demod_coeffs(c.ctypes.data_as(C.c_void_p), c.size, C.byref(n)), "sdr_demod_coeffs")
+    return c
 
 
 def fmpll(out, x, freq, Fs, state, ncoScale=1.0, phaseAdjust=0.0, normBandwidth=0.01, stream=None):

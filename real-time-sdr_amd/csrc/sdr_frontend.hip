@@ -4,6 +4,7 @@
 // Exact mode (k_frontend2): the reference's f32 products and sums in tap order, f64 discriminator
 // division. Fast mode (k_frontend_mfma): the FIR as an int8 Toeplitz GEMM on the matrix cores.
 #include "sdr_internal.h"
+#include "demod_phase.h"
 
 #include <hip/hip_ext.h>
 
@@ -30,6 +31,8 @@ namespace {
 // State: tail = last (ntaps-1) I/Q pairs of the previous block (u8, 128 == 0.0f),
 //        prev = last decimated (I, Q) of the previous block. Both double-buffered by parity.
 // ------------------------------------------------------------------------------------------
+// PH: the phase discriminator (SDR_FLAG_PHASE_DEMOD, demod_phase.h) instead of demod.cpp:8-19.
+template <bool PH>
 __global__ __launch_bounds__(BLK) void k_frontend(
     const uint8_t* __restrict__ iq, size_t iq_stride, const uint8_t* __restrict__ tail_in,
     uint8_t* __restrict__ tail_out, const float2* __restrict__ prev_in, float2* __restrict__ prev_out,
@@ -77,7 +80,11 @@ __global__ __launch_bounds__(BLK) void k_frontend(
         const float2 cur = sds[n - c0];
         const float2 pv = (n == 0) ? prev_in[ch] : sds[n - 1 - c0];
         float r;
-        if ((cur.x == 0) & (cur.y == 0)) {
+        if constexpr (PH) {
+            float re, im;
+            demod_products(f32x2{cur.x, cur.y}, f32x2{pv.x, pv.y}, re, im);
+            r = demod_phase2(f32x2{re, re}, f32x2{im, im}).x;
+        } else if ((cur.x == 0) & (cur.y == 0)) {
             r = 0.0f;
         } else {
             const float num = cur.x * (cur.y - pv.y) - cur.y * (cur.x - pv.x);
@@ -422,8 +429,9 @@ __device__ __forceinline__ void fe_fir(const uint8_t* __restrict__ sw, const flo
 
 // The discriminator (demod.cpp:8-19) of lane t's R outputs c0 + t R + r and their stores into out
 // (fm_demod of the channel; c0 is the tile's carry output, never written); the block's last (I, Q)
-// goes to prev_out.
-template <int R>
+// goes to prev_out. PH: the phase discriminator (SDR_FLAG_PHASE_DEMOD, demod_phase.h) instead -- all
+// f32, two outputs per packed polynomial, none of the f64 reciprocal, tie key or division fallback.
+template <int R, bool PH>
 __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int ch, const float2* __restrict__ prev_in,
                                               float2* __restrict__ prev_out, float* __restrict__ out, int block_if) {
     // ---- discriminator (demod.cpp:8-19); the previous output of lane t's first comes from t-1
@@ -445,6 +453,18 @@ __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int
         }
         return pv;
     };
+    if constexpr (PH) {
+        static_assert(R % 2 == 0, "outputs are finished in pairs");
+#pragma unroll
+        for (int r = 0; r < R; r += 2) {
+            float re0, im0, re1, im1;
+            demod_products(acc[r], prev(r), re0, im0);
+            demod_products(acc[r + 1], prev(r + 1), re1, im1);
+            const f32x2 ph = demod_phase2(f32x2{re0, re1}, f32x2{im0, im1});
+            v[r] = ph.x;
+            v[r + 1] = ph.y;
+        }
+    } else {                                         // the reference's discriminator (its lines keep their indentation)
 #if SDR_FE_DISC
     // The reference's value is RN32(RN64(num / den)), den = RN64(I^2 + Q^2) (pow(x, 2.0) is exact
     // in f64, so den is one fma). Instead of the IEEE f64 division: q = RN64(num * r1), r1 = 1/den
@@ -485,6 +505,7 @@ __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int
             }
         }
     }
+    }                                                // if constexpr (PH) .. else
 #endif
     if (t > 0 && cbase + R < block_if) {             // all R outputs written, none the block's last
         if ((reinterpret_cast<uintptr_t>(out + cbase) & 7) == 0) {
@@ -511,7 +532,7 @@ __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int
 // last runs into the padding, u8 128 = 0.0f) stage per dword from the block, the tail or the pad.
 // Tiles j0 .. j0+jn-1 of every channel (blockIdx.x = ch*jn + j - j0): the whole block (j0 = 0, jn =
 // tiles per channel) or one part of it (sdr_frontend_pre_parts, the pipeline fill).
-template <int R, int D>
+template <int R, int D, bool PH>
 __global__ __launch_bounds__(64) void k_frontend2(
     const uint8_t* __restrict__ iq, size_t iq_stride, const uint8_t* __restrict__ tail_in,
     uint8_t* __restrict__ tail_out, const float2* __restrict__ prev_in, float2* __restrict__ prev_out,
@@ -593,7 +614,7 @@ __global__ __launch_bounds__(64) void k_frontend2(
     __syncthreads();
     f32x2 acc[R];
     fe_fir<R, D>(sw, hs, acc);
-    fe_disc_store<R>(acc, c0, ch, prev_in, prev_out, fm + (size_t)ch * fm_stride, block_if);
+    fe_disc_store<R, PH>(acc, c0, ch, prev_in, prev_out, fm + (size_t)ch * fm_stride, block_if);
     float* out = fm + (size_t)ch * fm_stride;
     if (j == 0) {
         const uint16_t* last = reinterpret_cast<const uint16_t*>(src) + (block_iq - HP);
@@ -698,7 +719,7 @@ __device__ __forceinline__ void tn_fir(const float* __restrict__ sy, const float
 }
 
 // tune[pos] = {channel, source row, khz mod N, 1: this channel stores its row's tail}
-template <int R, int D>
+template <int R, int D, bool PH>
 __global__ __launch_bounds__(64) void k_frontend_tuned(
     const uint8_t* __restrict__ iq, size_t iq_stride, const uint8_t* __restrict__ tail_in,
     uint8_t* __restrict__ tail_out, const float2* __restrict__ prev_in, float2* __restrict__ prev_out,
@@ -801,7 +822,7 @@ __global__ __launch_bounds__(64) void k_frontend_tuned(
     f32x2 acc[R];
     tn_fir<R, D>(reinterpret_cast<const float*>(sy4), hs, acc);
     float* out = fm + (size_t)ch * fm_stride;
-    fe_disc_store<R>(acc, c0, ch, prev_in, prev_out, out, block_if);
+    fe_disc_store<R, PH>(acc, c0, ch, prev_in, prev_out, out, block_if);
     if (j == 0) {
         if (tn.w) {                                   // one channel per source row keeps the row's tail
             const uint16_t* last = reinterpret_cast<const uint16_t*>(src) + (block_iq - HP);
@@ -848,8 +869,8 @@ int frontend_launch(const FrontendArgs& a, hipStream_t s, int j0, int jn) {
     // (a.stamps); the generic kernel records HIP events with the launch (hipExtLaunchKernelGGL: the
     // start event is a marker ahead of the dispatch, so its span exceeds the kernel's by the marker's
     // latency, ~9 us)
-#define FE2(DD)                                                                                               \
-    hipExtLaunchKernelGGL((k_frontend2<FE_R, DD>), g2, dim3(64), 0, s, a.ev0, a.ev1, 0, iq, iq_stride, tail_in, \
+#define FE2(DD, PP)                                                                                           \
+    hipExtLaunchKernelGGL((k_frontend2<FE_R, DD, PP>), g2, dim3(64), 0, s, a.ev0, a.ev1, 0, iq, iq_stride, tail_in, \
                           tail_out, prev_in, prev_out, a.hs, a.block_iq, a.block_if, fm_p, fm_o, a.fm_stride, j0, jn, \
                           a.pad80, a.stamps)
     if (a.fast) {
@@ -868,19 +889,22 @@ int frontend_launch(const FrontendArgs& a, hipStream_t s, int j0, int jn) {
         else { if (x4) FEM(3, true); else FEM(3, false); }
 #undef FEM
     } else if (a.ntaps == 101 && a.D == 10) {
-        FE2(10);
+        if (a.phase) FE2(10, true); else FE2(10, false);
     } else if (a.ntaps == 101 && a.D == 4) {
-        FE2(4);
+        if (a.phase) FE2(4, true); else FE2(4, false);
     } else if (a.ntaps == 101 && a.D == 3) {
-        FE2(3);
+        if (a.phase) FE2(3, true); else FE2(3, false);
     } else {
         if (j0 != 0 || jn != tiles_ch) return fail(SDR_E_INVALID, "frontend: parts need 101 taps");
         const int tile = FIR_TILE;
         dim3 grid(cdiv(a.block_if, tile), a.nch);
         const size_t lds = frontend_lds_bytes(a.ntaps, tile, a.D);
-        hipExtLaunchKernelGGL(k_frontend, grid, dim3(BLK), (uint32_t)lds, s, a.ev0, a.ev1, 0, iq, iq_stride, tail_in,
-                              tail_out, prev_in, prev_out, a.h, a.ntaps, a.D, a.block_iq, a.block_if, tile, fm_p, fm_o,
-                              a.fm_stride);
+#define FEG(PP)                                                                                               \
+        hipExtLaunchKernelGGL(k_frontend<PP>, grid, dim3(BLK), (uint32_t)lds, s, a.ev0, a.ev1, 0, iq, iq_stride,     \
+                              tail_in, tail_out, prev_in, prev_out, a.h, a.ntaps, a.D, a.block_iq, a.block_if, tile,   \
+                              fm_p, fm_o, a.fm_stride)
+        if (a.phase) FEG(true); else FEG(false);
+#undef FEG
     }
 #undef FE2
     LAUNCH_CHECK();
@@ -905,13 +929,13 @@ int frontend_tuned_launch(const FrontendArgs& a, const float* ht, const float* q
     const int tiles = tuned_tiles(a.block_if), total = tiles * a.nch, per = cdiv(total, nxcc);
     const dim3 g(per * nxcc);
     const int4* tn = reinterpret_cast<const int4*>(tune);
-#define FET(DD)                                                                                                   \
-    hipLaunchKernelGGL((k_frontend_tuned<TN_R, DD>), g, dim3(64), 0, s, a.iq, a.iq_stride, a.tail_in, a.tail_out,    \
+#define FET(DD, PP)                                                                                               \
+    hipLaunchKernelGGL((k_frontend_tuned<TN_R, DD, PP>), g, dim3(64), 0, s, a.iq, a.iq_stride, a.tail_in, a.tail_out,    \
                        a.prev_in, a.prev_out, ht, qtab, tn, phase0, a.block_iq, a.block_if, a.fm, a.fm_other,         \
                        a.fm_stride, tiles, total, per, nxcc, a.pad80, a.stamps)
-    if (a.D == 10) FET(10);
-    else if (a.D == 4) FET(4);
-    else FET(3);
+    if (a.D == 10) { if (a.phase) FET(10, true); else FET(10, false); }
+    else if (a.D == 4) { if (a.phase) FET(4, true); else FET(4, false); }
+    else { if (a.phase) FET(3, true); else FET(3, false); }
 #undef FET
     LAUNCH_CHECK();
     return SDR_OK;

@@ -106,6 +106,7 @@ struct FrontendArgs {
     double yscale;             // MFMA fixed-point scale
     const uint32_t* pad80;     // 64 words of u8 128
     bool fast;
+    bool phase;                // SDR_FLAG_PHASE_DEMOD: the phase discriminator (exact front ends only)
     hipEvent_t ev0, ev1;       // non-null: HIP events recorded with the launch (sdr_frontend_timing)
     unsigned long long* stamps;   // non-null (k_frontend2): [workgroup][start, end] on the 100 MHz clock
 };

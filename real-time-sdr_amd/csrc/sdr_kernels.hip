@@ -32,6 +32,7 @@
 #include "sdr_amd.h"
 #include "pll_math.h"
 #include "nco.h"
+#include "demod_phase.h"
 
 #pragma clang fp contract(off)
 
@@ -1199,6 +1200,8 @@ __global__ void k_state_update(float* __restrict__ state, int nstate, const floa
 }
 
 // fmDemodNoArctan over separate I/Q arrays (demod.cpp:3-24); prev updated by k_demod_prev.
+// PH: the phase discriminator instead (sdr_fm_demod_phase, demod_phase.h).
+template <bool PH>
 __global__ __launch_bounds__(BLK) void k_demod(float* __restrict__ out, size_t out_stride,
                                                const float* __restrict__ I, const float* __restrict__ Q,
                                                size_t iq_stride, int n, const float2* __restrict__ prev) {
@@ -1210,7 +1213,11 @@ __global__ __launch_bounds__(BLK) void k_demod(float* __restrict__ out, size_t o
     const float ci = Ic[i], cq = Qc[i];
     const float2 pv = (i == 0) ? prev[ch] : make_float2(Ic[i - 1], Qc[i - 1]);
     float r;
-    if ((ci == 0) & (cq == 0)) {
+    if constexpr (PH) {
+        float re, im;
+        demod_products(f32x2{ci, cq}, f32x2{pv.x, pv.y}, re, im);
+        r = demod_phase2(f32x2{re, re}, f32x2{im, im}).x;
+    } else if ((ci == 0) & (cq == 0)) {
         r = 0.0f;
     } else {
         const float num = ci * (cq - pv.y) - cq * (ci - pv.x);
@@ -1809,6 +1816,8 @@ extern "C" int sdr_diag_pll_hwid(unsigned long long* out, int nmax) { return dia
 int sdr_ctx_create(sdr_ctx** out, int device, int nch, int mode, int rds_on, int flags) {
     if (!out || nch <= 0) return fail(SDR_E_INVALID, "bad arguments");
     *out = nullptr;
+    if ((flags & SDR_FLAG_FAST_FRONTEND) && (flags & SDR_FLAG_PHASE_DEMOD))
+        return fail(SDR_E_INVALID, "SDR_FLAG_PHASE_DEMOD needs the exact front end (not SDR_FLAG_FAST_FRONTEND)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0)
         return fail(SDR_E_NODEV, "no HIP device %d", device);
@@ -2064,6 +2073,7 @@ FrontendArgs frontend_args(const sdr_ctx* c, const uint8_t* iq, size_t iq_stride
     a.yscale = c->fe_yscale;
     a.pad80 = c->pad80;
     a.fast = (c->flags & SDR_FLAG_FAST_FRONTEND) != 0 && c->fe_afrag != nullptr;
+    a.phase = (c->flags & SDR_FLAG_PHASE_DEMOD) != 0;
     return a;
 }
 // Parity release across streams (threadsafequeue.h:29-31: a producer reuses a buffer only after its
@@ -3242,15 +3252,37 @@ int sdr_convolve_fir_resample(float* y, size_t y_stride, const float* x, size_t 
     return SDR_OK;
 }
 
-int sdr_fm_demod(float* out, size_t out_stride, const float* I, const float* Q, size_t iq_stride, int nch, int n,
-                 float* prev, void* stream) {
+extern "C++" {
+template <bool PH>
+static int fm_demod_launch(float* out, size_t out_stride, const float* I, const float* Q, size_t iq_stride, int nch, int n,
+                           float* prev, void* stream) {
     if (!out || !I || !Q || !prev || nch <= 0 || n <= 0) return fail(SDR_E_INVALID, "fm_demod: bad arguments");
-    hipLaunchKernelGGL(k_demod, dim3(cdiv(n, BLK), nch), dim3(BLK), 0, S(stream), out, out_stride, I, Q, iq_stride, n,
-                       reinterpret_cast<const float2*>(prev));
+    hipLaunchKernelGGL(k_demod<PH>, dim3(cdiv(n, BLK), nch), dim3(BLK), 0, S(stream), out, out_stride, I, Q, iq_stride,
+                       n, reinterpret_cast<const float2*>(prev));
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_demod_prev, dim3(cdiv(nch, 64)), dim3(64), 0, S(stream), reinterpret_cast<float2*>(prev), I,
                        Q, iq_stride, n, nch);
     LAUNCH_CHECK();
+    return SDR_OK;
+}
+}  // extern "C++"
+
+int sdr_fm_demod(float* out, size_t out_stride, const float* I, const float* Q, size_t iq_stride, int nch, int n,
+                 float* prev, void* stream) {
+    return fm_demod_launch<false>(out, out_stride, I, Q, iq_stride, nch, n, prev, stream);
+}
+
+int sdr_fm_demod_phase(float* out, size_t out_stride, const float* I, const float* Q, size_t iq_stride, int nch, int n,
+                       float* prev, void* stream) {
+    return fm_demod_launch<true>(out, out_stride, I, Q, iq_stride, nch, n, prev, stream);
+}
+
+int sdr_demod_coeffs(float* c, int max, int* n) {
+    static const float k[SDR_DEMOD_K + 1] = {SDR_DEMOD_C0, SDR_DEMOD_C1, SDR_DEMOD_C2, SDR_DEMOD_C3,
+                                             SDR_DEMOD_C4, SDR_DEMOD_C5, SDR_DEMOD_C6, SDR_DEMOD_C7};
+    if (n) *n = SDR_DEMOD_K + 1;
+    if (c && max >= SDR_DEMOD_K + 1)
+        for (int i = 0; i <= SDR_DEMOD_K; i++) c[i] = k[i];
     return SDR_OK;
 }
 

@@ -311,6 +311,17 @@ int sdr_meter_status(int mode, const sdr_meter_row* row, const sdr_meter_opts* o
     return SDR_OK;
 }
 
+int sdr_meter_deviation(int mode, const sdr_meter_row* row, double* peak_khz, double* rms_khz, double* offset_khz) {
+    sdr_info in;
+    if (const int r = mode_info(&in, 1, mode, 1)) return r;
+    if (!row) return fail(SDR_E_INVALID, "meter_deviation: null row");
+    const double n = in.block_if, k = (double)in.if_Fs / (2.0 * 3.14159265358979323846) / 1000.0;
+    if (peak_khz) *peak_khz = (double)row->fm_peak * k;
+    if (rms_khz) *rms_khz = std::sqrt((double)row->fm_sq / n) * k;
+    if (offset_khz) *offset_khz = (double)row->fm_sum / n * k;
+    return SDR_OK;
+}
+
 int sdr_meter_create(sdr_meter** out, int device, int nch, int mode) {
     if (!out) return fail(SDR_E_INVALID, "meter_create: out is NULL");
     *out = nullptr;

@@ -2,7 +2,7 @@
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
 //   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
-//             [--deemph US] [--blend]
+//             [--deemph US] [--blend] [--demod ref|phase]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //   sdr_multi NCH --wide W [--shift S] --tune FILE ...          (the receiver on wide captures)
 //   sdr_multi NWIDE --wide W [--shift S] --scan ...             (the scan of wide captures)
@@ -33,6 +33,9 @@
 // block; with --scan NWIDE wide streams are scanned and PREFIX.stations names the capture rows, so
 // `sdr_multi <n> --wide W --tune PREFIX.stations` receives what `sdr_multi NWIDE --wide W --scan` found.
 // The summary line counts the wide bytes read; clip counts go to stderr when any are non-zero.
+// --demod phase: the phase discriminator (SDR_FLAG_PHASE_DEMOD, include/sdr_amd.h) instead of the
+// reference's (--demod ref, the default): the audio of a loud station no longer folds, and with --meter every
+// PREFIX.status line also ends with the run's peak deviation and mean offset in kHz. Not with --fast.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -51,7 +54,7 @@
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
-                         "[--tune FILE] [--meter] [--deemph US] [--blend]\n"
+                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
                          "       sdr_multi NCH --wide W [--shift S] --tune FILE ...   |   sdr_multi NWIDE --wide W [--shift S] --scan ...\n"
@@ -59,6 +62,8 @@ namespace {
                          "  --meter: also write PREFIX.meter (64-byte readings per channel and block) and PREFIX.status\n"
                          "  --deemph US: also write PREFIX.audio, the PCM de-emphasised with 0, 50 or 75 microseconds\n"
                          "  --blend: PREFIX.audio blended to mono where the meter finds no pilot (needs --meter)\n"
+                         "  --demod phase: the phase discriminator (fm_demod in radians, no fold above if_Fs/4 of deviation;\n"
+                         "            PREFIX.status gains peak_khz and offset_khz); ref (default): the reference's; not with --fast\n"
                          "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n"
                          "  --wide W: the input is wide int8 I/Q at W (4, 8, 10) times rf_Fs, rows of 2*W*block_iq bytes, each\n"
                          "            split into 2W-1 capture rows (--shift S: output shift 1-24); needs --tune or --scan\n");
@@ -107,8 +112,15 @@ int main(int argc, char** argv) {
         else if (a == "--step" && i + 1 < argc) so.pick.step_khz = std::atoi(argv[++i]);
         else if (a == "--thr" && i + 1 < argc) so.pick.thr_db = (float)std::atof(argv[++i]);
         else if (a == "--fast") o.flags |= SDR_FLAG_FAST_FRONTEND;
+        else if (a == "--demod" && i + 1 < argc) {
+            const std::string d = argv[++i];
+            if (d == "phase") o.flags |= SDR_FLAG_PHASE_DEMOD;
+            else if (d == "ref") o.flags &= ~SDR_FLAG_PHASE_DEMOD;
+            else usage();
+        }
         else usage();
     }
+    if ((o.flags & SDR_FLAG_FAST_FRONTEND) && (o.flags & SDR_FLAG_PHASE_DEMOD)) usage();   // the MFMA front end has none
     if (const char* dev = std::getenv("SDR_DEVICE")) o.device = std::atoi(dev);
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();

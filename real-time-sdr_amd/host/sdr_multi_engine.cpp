@@ -98,6 +98,7 @@ struct RunSpec {
 bool validate(const RunSpec& r) {
     const sdr_multi_opts* o = r.o;
     if (!o || (r.blend && (!r.meter || !r.audio))) return false;
+    if ((o->flags & SDR_FLAG_FAST_FRONTEND) && (o->flags & SDR_FLAG_PHASE_DEMOD)) return false;   // sdr_ctx_create's rule
     if (r.audio) {   // what sdr_audio_create would refuse
         float a = 0.0f, b = 0.0f;
         if (sdr_audio_coeffs(o->mode, r.audio->tau_us, &a, &b) != SDR_OK || !(r.audio->blend_hi > r.audio->blend_lo)) return false;
@@ -405,6 +406,7 @@ struct MeterOut {
     sdr_meter* m = nullptr;
     sdr_meter_opts mo{};
     int nch = 0, mode = 0;
+    bool phase = false;                  // SDR_FLAG_PHASE_DEMOD: the rows' fm fields are radians (sdr_meter_deviation)
     Pinned<uint8_t> h_rows[2][NH];       // per consumer and rotation slot: nch rows
     File f;                              // PREFIX.meter
     std::mutex mu;
@@ -413,9 +415,11 @@ struct MeterOut {
     struct Sum {
         double v[5] = {};                // offset, level_db, pilot_nr, rds_nr, eye_db
         long long flag[4] = {};          // blocks with STEREO, RDS, OFFTUNE, DEAD_AIR
+        double peak_khz = 0.0, offset_khz = 0.0;   // a phase run: the maximum and the sum over the blocks
     };
     std::vector<Sum> sum;
-    MeterOut(const sdr_multi_opts& o, const sdr_meter_opts& opts, bool cache) : mo(opts), nch(o.nch), mode(o.mode), sum((size_t)o.nch) {
+    MeterOut(const sdr_multi_opts& o, const sdr_meter_opts& opts, bool cache) : mo(opts), nch(o.nch), mode(o.mode),
+          phase((o.flags & SDR_FLAG_PHASE_DEMOD) != 0), sum((size_t)o.nch) {
         check_sdr(sdr_meter_create(&m, o.device, o.nch, o.mode), "sdr_meter_create");
         for (auto& per : h_rows)
             for (auto& p : per) p.take((size_t)nch * sizeof(sdr_meter_row), cache);
@@ -456,6 +460,12 @@ struct MeterOut {
             const double v[5] = {st.offset, st.level_db, st.pilot_nr, st.rds_nr, st.eye_db};
             for (int i = 0; i < 5; i++) s.v[i] += v[i];
             for (int i = 0; i < 4; i++) s.flag[i] += (st.flags >> i) & 1;
+            if (phase) {
+                double pk = 0.0, off = 0.0;
+                check_sdr(sdr_meter_deviation(mode, &o, &pk, nullptr, &off), "sdr_meter_deviation");
+                s.peak_khz = std::max(s.peak_khz, pk);
+                s.offset_khz += off;
+            }
         }
         other.pop_front();
         blocks++;
@@ -477,7 +487,9 @@ struct MeterOut {
                     std::fprintf(t, "%c%s", any ? '|' : ' ', names[i]);
                     any = true;
                 }
-            std::fprintf(t, "%s\n", any ? "" : " -");
+            std::fprintf(t, "%s", any ? "" : " -");
+            if (phase) std::fprintf(t, " peak_khz %.2f offset_khz %.3f", s.peak_khz, s.offset_khz / n);
+            std::fprintf(t, "\n");
         }
     }
 };
