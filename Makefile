@@ -14,7 +14,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-g
 LIB      := $(PKG)/libsdr_amd.so
 SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_scan.hip \
             $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip $(PKG)/csrc/sdr_split.hip \
-            $(PKG)/csrc/sdr_taps.cpp
+            $(PKG)/csrc/sdr_rds.hip $(PKG)/csrc/sdr_taps.cpp $(PKG)/csrc/sdr_rds_text.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
 HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h $(PKG)/csrc/demod_phase.h
 
@@ -26,7 +26,7 @@ HOSTSRCS  := $(PKG)/host/dropin_primitives.cpp $(PKG)/host/dropin_stages.cpp $(P
              $(PKG)/host/sdr_multi_engine.cpp $(PKG)/host/sdr_scan_run.cpp
 HOSTHDRS  := $(wildcard include/dropin/*.h) $(PKG)/host/hip_util.h include/sdr_amd.h include/sdr_multi.h \
              include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h \
-             include/sdr_multi_wide.h include/sdr_wide_scan.h
+             include/sdr_multi_wide.h include/sdr_wide_scan.h include/sdr_multi_rds.h
 CLI       := $(PKG)/bin/sdr_project
 MULTI     := $(PKG)/bin/sdr_multi
 
@@ -65,7 +65,7 @@ $(CLI): $(PKG)/host/sdr_project.cpp $(HOSTLIB)
 	@mkdir -p $(dir $@)
 	$(CXX) $(HOSTFLAGS) -o $@ $< -L$(PKG) -lsdr_host -Wl,-rpath,'$$ORIGIN/..'
 
-$(MULTI): $(PKG)/host/sdr_multi.cpp include/sdr_multi.h include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h include/sdr_multi_wide.h include/sdr_wide_scan.h $(HOSTLIB)
+$(MULTI): $(PKG)/host/sdr_multi.cpp include/sdr_multi.h include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h include/sdr_multi_wide.h include/sdr_wide_scan.h include/sdr_multi_rds.h $(HOSTLIB)
 	@mkdir -p $(dir $@)
 	$(CXX) $(HOSTFLAGS) -o $@ $< -L$(PKG) -lsdr_host -lsdr_amd -L$(ROCM)/lib -lamdhip64 \
 	    -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,$(ROCM)/lib

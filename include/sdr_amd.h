@@ -458,6 +458,109 @@ int sdr_audio_finish(sdr_audio *a, const int16_t *in, size_t in_stride, int16_t 
 /* host [nch]; synchronises `stream` */
 int sdr_audio_read_state(sdr_audio *a, sdr_audio_state *host, void *stream);
 
+/* ---- RDS group decoder (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
+ * block synchronisation with a flywheel, +-1 bit slip recovery and burst-error correction over the bits
+ * sdr_rds_bits wrote, per channel on the GPU, and a host text layer over the 16-byte group records. All
+ * integer; tests/rds_model.py defines every bit, DESIGN.md section 4g explains the rules.
+ * Coding (IEC 62106): g(x) = 0x5B9; the syndrome of a 26-bit word (first bit received = bit 25) is its
+ * remainder modulo g; offset words A, B, C, C', D = 0x0FC, 0x198, 0x168, 0x350, 0x1B4 of block indices
+ * 0, 1, 2, 2, 3; a word matches offset o when its syndrome equals the offset word.
+ * Correction table: every error pattern e whose set bits span at most max_burst of the 26 positions,
+ * tab[syndrome(e)] = e (51 entries at max_burst 2, 367 at 5, all syndromes distinct), 0 elsewhere.
+ * Per channel and bit i (counted from the last reset), after shifting it in:
+ *   not synchronised, from the 26th bit on: a latest-26 word that matches an offset of block index idx is a
+ *     hit. With a pending hit (p, q), d = i - p, d % 26 == 0, 1 <= d / 26 <= 4 and (q + d / 26) % 4 == idx,
+ *     sync is acquired: the assembly is cleared, this block is placed as a good block of expect = idx, the
+ *     end-of-block step runs, the next judgement is at i + 27, no hit is pending. Else the hit is pending.
+ *   synchronised, at i == judge_at only (one bit after the block's nominal end), the first that holds:
+ *     1 nominal (bits i-26 .. i-1) matches an offset of block expect (C before C'): good, next at i + 26
+ *     2 early (i-27 .. i-2) matches: good, a slip, next at i + 25
+ *     3 late (i-25 .. i) matches: good, a slip, next at i + 27
+ *     4 syndrome(nominal) ^ offset word is in the table: the word is corrected; bad_run stays; next at i + 26
+ *     5 bad: bad_run + 1, next at i + 26; bad_run == loss_blocks: sync is lost, the pending hit and the
+ *       assembly are cleared and the end-of-block step does not run
+ *     (1-3 set bad_run = 0 and the block's bit in ok; 4 sets it in ok and corrected)
+ *   end of block: expect == 3 with ok != 0 emits a group; expect == 3 clears the assembly; expect + 1 mod 4.
+ * A call: nbits[ch] in 0 .. SDR_MAX_BITS consumes that many 0/1 bytes of the channel's row; -1, and
+ * anything else but SDR_NBITS_POISONED, consumes nothing and changes nothing; SDR_NBITS_POISONED (bits are
+ * missing) drops sync if there is one (lost + 1) and clears the pending hit and the assembly. The result
+ * does not depend on how a channel's stream is cut into calls. */
+#define SDR_RDS_MAX_GROUPS 4     /* per channel and call (256 bits hold at most three) */
+typedef struct sdr_rds_group {   /* 16 bytes */
+    uint16_t w[4];               /* the information words of blocks A..D, 0 where the block is not in ok */
+    uint8_t ok, corrected;       /* bit b: block b was received (ok), by correction (corrected) */
+    uint8_t flags;               /* SDR_RDS_GROUP_CPRIME */
+    uint8_t reserved;            /* 0 */
+    uint32_t bits;               /* the low 32 bits of the count of bits consumed when it was emitted */
+} sdr_rds_group;
+#define SDR_RDS_GROUP_CPRIME 0x1 /* block C carried offset C' */
+typedef struct sdr_rds_stats {   /* 32 bytes */
+    uint32_t good, corrected, bad, slips, acquired, lost, groups, synced;
+} sdr_rds_stats;
+typedef struct sdr_rds_opts {
+    int max_burst, loss_blocks;  /* 0..5, 1..64 */
+} sdr_rds_opts;
+void sdr_rds_opts_default(sdr_rds_opts *o);   /* 2, 8 */
+/* host only, no GPU */
+uint32_t sdr_rds_syndrome(uint32_t w26);
+/* tab1024 may be NULL; *entries = the number of patterns */
+int sdr_rds_correction_table(int max_burst, uint32_t *tab1024, int *entries);
+/* 1 when the mode's RDS chain recovers bits at 1187.5 bit/s -- its baseband rate if_Fs 247 / 640 is
+ * 2375 symbol_Fs samples a second: mode 0 -- and 0 otherwise (modes 1 to 3, whose bits carry no groups) */
+int sdr_rds_mode_ok(int mode);
+/* device: the decoder is its own handle, like the meter. sdr_rds_groups enqueues one kernel (one wave per
+ * channel) on `stream`; nbits_dev [nch] int32 and bits_dev [nch][bits_stride] are device arrays of
+ * sdr_rds_bits' layout, ordered before it by the caller (the same stream does). Each call overwrites the
+ * handle's groups [nch][SDR_RDS_MAX_GROUPS] and ngroups [nch]; the _read calls copy them (or the counters)
+ * to the host and synchronise `stream`. SDR_E_INVALID, nothing enqueued: NULL handles or pointers, nch < 1,
+ * options out of range, bits_stride < SDR_MAX_BITS. */
+typedef struct sdr_rds_dec sdr_rds_dec;
+int sdr_rds_dec_create(sdr_rds_dec **out, int device, int nch, const sdr_rds_opts *opts);
+int sdr_rds_dec_destroy(sdr_rds_dec *d);
+int sdr_rds_dec_reset(sdr_rds_dec *d, void *stream);
+int sdr_rds_groups(sdr_rds_dec *d, const int32_t *nbits_dev, const uint8_t *bits_dev, size_t bits_stride, void *stream);
+int sdr_rds_groups_read(sdr_rds_dec *d, sdr_rds_group *host_groups, int32_t *host_ngroups, void *stream);
+int sdr_rds_stats_read(sdr_rds_dec *d, sdr_rds_stats *host_stats, void *stream);
+/* sdr_rds_groups_read without the synchronisation, for a caller that orders the copies with an event of
+ * its own (the receiver engine); the host buffers should be pinned */
+int sdr_rds_groups_copy(sdr_rds_dec *d, sdr_rds_group *host_groups, int32_t *host_ngroups, void *stream);
+
+/* The text layer (host only, plain C++, no GPU): what a station says, from its group records. A block is
+ * used only when its ok bit is set. PI: block A, reported once two groups in a row agree. PTY, TP: block B.
+ * Groups 0A/0B: TA, MS, and with block D the PS segment (complete when all four segments were seen since a
+ * seen segment last changed); 0A's block C holds two AF codes: 1..204 = 87.6 + 0.1 code MHz, 224..249 the
+ * list length (a new list), others ignored; up to 25 frequencies. 2A/2B: RadioText of 64 / 32 characters
+ * (2A: blocks C and D, 2B: D), cleared when the A/B flag changes, ended by 0x0D. 4A: clock time, MJD to
+ * y-m-d by the standard's formula, UTC hour and minute, local offset in half hours. Other group types are
+ * counted only. Characters 0x20..0x7E are ASCII, everything else prints as '.' (the upper half of the RDS
+ * character table is out of scope). */
+typedef struct sdr_rds_station {
+    uint16_t pi, pi_last;
+    uint8_t pi_valid, pi_seen;           /* pi_valid: pi is reported; pi_seen: pi_last holds a value */
+    uint8_t pty, tp, ta, ms, have_b, have_0;
+    uint8_t ps[8], ps_seen, ps_complete; /* ps_seen: segment mask */
+    uint8_t ps_done[8];                  /* the last complete name */
+    uint8_t rt[64], rt_ab, rt_have_ab, rt_len;   /* rt_len: 64 or 32 by the last 2A / 2B */
+    uint64_t rt_seen;                    /* character mask */
+    uint8_t ct_valid, ct_hour, ct_minute, ct_month, ct_day;
+    int8_t ct_offset;                    /* half hours, signed */
+    int32_t ct_year, ct_mjd;
+    uint8_t af_n, af_expect;             /* frequencies held, the list length last announced */
+    uint16_t af[25];                     /* in 100 kHz: 876 + code */
+    uint32_t hist[32];                   /* groups by type: 2 * type + version (needs block B) */
+    uint32_t ngroups;
+    uint32_t good, corrected, bad, slips, acquired, lost;   /* sdr_rds_station_stats */
+} sdr_rds_station;
+void sdr_rds_station_init(sdr_rds_station *s);
+void sdr_rds_station_update(sdr_rds_station *s, const sdr_rds_group *g);
+void sdr_rds_station_stats(sdr_rds_station *s, const sdr_rds_stats *st);
+/* BLER = bad / (good + corrected + bad), 0 with no blocks */
+double sdr_rds_station_bler(const sdr_rds_station *s);
+/* the RBDS programme-type name the receiver prints (rds.cpp's table) */
+const char *sdr_rds_pty_name(int pty);
+/* a multi-line report into buf (always terminated when n > 0); returns the length it needs */
+size_t sdr_rds_station_format(const sdr_rds_station *s, char *buf, size_t n);
+
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */

@@ -1,0 +1,44 @@
+/* sdr_multi_rds.h -- the multi-channel receiver engine (include/sdr_multi.h) with the RDS group decoder
+ * (include/sdr_amd.h, sdr_rds_*): block synchronisation, slip recovery and burst correction on the GPU
+ * where the bits are, and what every station says. Same engine, same options and statistics, exported
+ * from libsdr_host.so; the CLI's --rds-decode [--rds-correct N] calls it.
+ *
+ * The RDS thread runs sdr_rds_groups behind its sdr_rds_bits on its post stream, copies the block's group
+ * records out with the bits into pinned buffers of the engine's pool, and its frame layer feeds one
+ * sdr_rds_station per channel. The PCM, the RDS text, the captures and the meter's and the finishing
+ * stage's files are those of a run without the decoder. With an out_prefix the run also writes
+ *   PREFIX.groups   one text line per group, block after block, the channels in order within a block:
+ *                     ch <c> bits <n> AAAA BBBB CCCC DDDD
+ *                   <n> = sdr_rds_group.bits; a block that is not in ok is "----", a corrected block has
+ *                   a trailing "*"
+ *   PREFIX.radio    at the end, every channel's sdr_rds_station_format report, each line behind
+ *                   "ch <c>: ": PI, PTY (the RBDS names), TP/TA/MS, PS, RT, CT, AF, the groups by type,
+ *                   blocks good/corrected/bad and BLER, slips, syncs acquired/lost. */
+#ifndef SDR_MULTI_RDS_H
+#define SDR_MULTI_RDS_H
+
+#include "sdr_amd.h"
+#include "sdr_multi.h"
+#include "sdr_multi_tuned.h"
+#include "sdr_multi_wide.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct sdr_multi_rds {
+    int max_burst, loss_blocks;   /* sdr_rds_opts: 0..5 and 1..64 */
+} sdr_multi_rds;
+
+/* sdr_multi_run_wide with the decoder: any of wide, tune, mo, ao may be NULL as there; rds == NULL is
+ * that call. SDR_E_INVALID, before anything starts, also for options out of range and for a mode whose
+ * RDS chain has no 1187.5 bit/s clock (sdr_rds_mode_ok: modes 1 to 3). */
+int sdr_multi_run_rds(const sdr_multi_opts *opts, const sdr_multi_wide *wide, const sdr_multi_tuning *tune,
+                      const sdr_meter_opts *mo, const sdr_audio_opts *ao, int blend, const sdr_multi_rds *rds,
+                      sdr_multi_stats *stats);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -89,6 +89,37 @@ class AudioState(C.Structure):
     _fields_ = [("y", C.c_float * 2)] + [(n, C.c_float) for n in ("blend", "gain", "blend_target", "gain_target")]
 
 
+class RdsGroup(C.Structure):
+    """sdr_rds_group: one RDS group as the decoder emits it, 16 bytes."""
+    _fields_ = [("w", C.c_uint16 * 4), ("ok", C.c_uint8), ("corrected", C.c_uint8), ("flags", C.c_uint8),
+                ("reserved", C.c_uint8), ("bits", C.c_uint32)]
+
+
+class RdsStats(C.Structure):
+    """sdr_rds_stats: one channel's block and sync counters, 32 bytes."""
+    _fields_ = [(n, C.c_uint32) for n in ("good", "corrected", "bad", "slips", "acquired", "lost", "groups", "synced")]
+
+
+class RdsOpts(C.Structure):
+    """sdr_rds_opts: the burst length the decoder corrects and the bad blocks in a row that end a sync."""
+    _fields_ = [("max_burst", C.c_int), ("loss_blocks", C.c_int)]
+
+
+class RdsStationC(C.Structure):
+    """sdr_rds_station: the text layer's state of one station."""
+    _fields_ = [("pi", C.c_uint16), ("pi_last", C.c_uint16), ("pi_valid", C.c_uint8), ("pi_seen", C.c_uint8),
+                ("pty", C.c_uint8), ("tp", C.c_uint8), ("ta", C.c_uint8), ("ms", C.c_uint8), ("have_b", C.c_uint8),
+                ("have_0", C.c_uint8), ("ps", C.c_uint8 * 8), ("ps_seen", C.c_uint8), ("ps_complete", C.c_uint8),
+                ("ps_done", C.c_uint8 * 8), ("rt", C.c_uint8 * 64), ("rt_ab", C.c_uint8), ("rt_have_ab", C.c_uint8),
+                ("rt_len", C.c_uint8), ("rt_seen", C.c_uint64), ("ct_valid", C.c_uint8), ("ct_hour", C.c_uint8),
+                ("ct_minute", C.c_uint8), ("ct_month", C.c_uint8), ("ct_day", C.c_uint8), ("ct_offset", C.c_int8),
+                ("ct_year", C.c_int32), ("ct_mjd", C.c_int32), ("af_n", C.c_uint8), ("af_expect", C.c_uint8),
+                ("af", C.c_uint16 * 25), ("hist", C.c_uint32 * 32), ("ngroups", C.c_uint32)] + \
+               [(n, C.c_uint32) for n in ("good", "corrected", "bad", "slips", "acquired", "lost")]
+
+
+RDS_MAX_GROUPS = 4
+RDS_GROUP_CPRIME = 0x1
 METER_ROW_AUDIO, METER_ROW_RDS = 0x1, 0x2                                   # MeterRow.flags
 METER_STEREO, METER_RDS, METER_OFFTUNE, METER_DEAD_AIR = 0x1, 0x2, 0x4, 0x8   # MeterState.flags
 
@@ -194,6 +225,23 @@ def lib() -> C.CDLL:
         "sdr_audio_blend_from_meter": ([vp, vp, vp], i32),
         "sdr_audio_finish": ([vp, vp, sz, vp, sz, vp], i32),
         "sdr_audio_read_state": ([vp, vp, vp], i32),
+        "sdr_rds_opts_default": ([C.POINTER(RdsOpts)], None),
+        "sdr_rds_syndrome": ([C.c_uint32], C.c_uint32),
+        "sdr_rds_correction_table": ([i32, vp, C.POINTER(i32)], i32),
+        "sdr_rds_mode_ok": ([i32], i32),
+        "sdr_rds_dec_create": ([C.POINTER(vp), i32, i32, C.POINTER(RdsOpts)], i32),
+        "sdr_rds_dec_destroy": ([vp], i32),
+        "sdr_rds_dec_reset": ([vp, vp], i32),
+        "sdr_rds_groups": ([vp, vp, vp, sz, vp], i32),
+        "sdr_rds_groups_read": ([vp, vp, vp, vp], i32),
+        "sdr_rds_groups_copy": ([vp, vp, vp, vp], i32),
+        "sdr_rds_stats_read": ([vp, vp, vp], i32),
+        "sdr_rds_station_init": ([C.POINTER(RdsStationC)], None),
+        "sdr_rds_station_update": ([C.POINTER(RdsStationC), C.POINTER(RdsGroup)], None),
+        "sdr_rds_station_stats": ([C.POINTER(RdsStationC), C.POINTER(RdsStats)], None),
+        "sdr_rds_station_bler": ([C.POINTER(RdsStationC)], C.c_double),
+        "sdr_rds_pty_name": ([i32], C.c_char_p),
+        "sdr_rds_station_format": ([C.POINTER(RdsStationC), C.c_char_p, sz], sz),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)
@@ -667,6 +715,145 @@ class AudioFinish:
         out = np.zeros(self.nch, audio_state_dtype())
         check(lib().sdr_audio_read_state(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_audio_read_state")
         return out
+
+
+# ------------------------------------------------------------------ RDS group decoder (include/sdr_amd.h, sdr_rds_*)
+def rds_group_dtype():
+    """numpy dtype of sdr_rds_group (16 bytes)."""
+    import numpy as np
+    return np.dtype(RdsGroup)
+
+
+def rds_stats_dtype():
+    """numpy dtype of sdr_rds_stats (32 bytes)."""
+    import numpy as np
+    return np.dtype(RdsStats)
+
+
+def rds_syndrome(w26: int) -> int:
+    """The 10-bit syndrome of a 26-bit RDS block (host only)."""
+    return int(lib().sdr_rds_syndrome(int(w26) & 0xFFFFFFFF))
+
+
+def rds_correction_table(max_burst: int = 2):
+    """(tab, entries): tab[syndrome] = the burst error pattern it corrects, 0 elsewhere (host only)."""
+    import numpy as np
+    tab = np.zeros(1024, np.uint32)
+    n = C.c_int(0)
+    check(lib().sdr_rds_correction_table(max_burst, tab.ctypes.data_as(C.c_void_p), C.byref(n)),
+          "sdr_rds_correction_table")
+    return tab, n.value
+
+
+def rds_opts(**opts) -> RdsOpts:
+    """The decoder's defaults (sdr_rds_opts_default) with the given fields replaced."""
+    o = RdsOpts()
+    lib().sdr_rds_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(RdsOpts._fields_):
+            raise SdrError(f"rds_opts: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+class RdsDecoder:
+    """The RDS group decoder of `nch` channels (sdr_rds_*): block sync with a flywheel, slip recovery and
+    burst correction on the GPU. Per block feed(nbits, bits) or feed_pipeline(pipe) after the pipeline's
+    rds(); groups() returns that call's group records. Its own handle; the state stays on the device."""
+
+    def __init__(self, nch: int, device: int = 0, max_burst: int = 2, loss_blocks: int = 8):
+        h = C.c_void_p()
+        o = rds_opts(max_burst=max_burst, loss_blocks=loss_blocks)
+        check(lib().sdr_rds_dec_create(C.byref(h), device, nch, C.byref(o)), "sdr_rds_dec_create")
+        self._h = h
+        self.nch, self.device = nch, device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sdr_rds_dec_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().sdr_rds_dec_reset(self._h, _stream(stream)), "sdr_rds_dec_reset")
+
+    def feed(self, nbits, bits, stream=None):
+        """One call: nbits int32 [nch] and bits uint8 [nch][>= SDR_MAX_BITS] device tensors."""
+        import torch
+        if nbits.dtype != torch.int32 or tuple(nbits.shape) != (self.nch,) or not nbits.is_contiguous():
+            raise ValueError(f"nbits must be a contiguous int32 [{self.nch}] tensor")
+        if bits.dtype != torch.uint8 or bits.dim() != 2 or bits.shape[0] != self.nch or bits.shape[1] < SDR_MAX_BITS:
+            raise ValueError(f"bits must be a uint8 [{self.nch}][>= {SDR_MAX_BITS}] tensor")
+        check(lib().sdr_rds_groups(self._h, _ptr(nbits), _ptr(bits), _row_stride(bits), _stream(stream)),
+              "sdr_rds_groups")
+
+    def feed_pipeline(self, pipe: "Pipeline", stream=None):
+        """The bits the pipeline's rds() / rds_bits() of the current block wrote (same stream)."""
+        self.feed(pipe.nbits, pipe.bits, stream)
+
+    def groups(self, stream=None):
+        """(groups [nch][RDS_MAX_GROUPS] of rds_group_dtype(), counts int32 [nch]) of the last call;
+        synchronises the stream."""
+        import numpy as np
+        g = np.zeros((self.nch, RDS_MAX_GROUPS), rds_group_dtype())
+        n = np.zeros(self.nch, np.int32)
+        check(lib().sdr_rds_groups_read(self._h, g.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p),
+                                        _stream(stream)), "sdr_rds_groups_read")
+        return g, n
+
+    def stats(self, stream=None):
+        """numpy structured array [nch] of rds_stats_dtype(); synchronises the stream."""
+        import numpy as np
+        out = np.zeros(self.nch, rds_stats_dtype())
+        check(lib().sdr_rds_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_rds_stats_read")
+        return out
+
+
+class RdsStation:
+    """The text layer of one station (sdr_rds_station_*, host only): update(groups) with records of
+    rds_group_dtype(), text() for the report; the fields are on .s (RdsStationC)."""
+
+    def __init__(self):
+        self.s = RdsStationC()
+        lib().sdr_rds_station_init(C.byref(self.s))
+
+    def update(self, groups):
+        import numpy as np
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(groups, rds_group_dtype())).reshape(-1))
+        base = a.ctypes.data
+        for k in range(a.shape[0]):
+            lib().sdr_rds_station_update(C.byref(self.s), C.cast(base + 16 * k, C.POINTER(RdsGroup)))
+
+    def set_stats(self, stats):
+        """One channel's counters (a record of rds_stats_dtype()) for the block error rate."""
+        import numpy as np
+        a = np.ascontiguousarray(np.asarray(stats, rds_stats_dtype()).reshape(-1)[:1])
+        lib().sdr_rds_station_stats(C.byref(self.s), C.cast(a.ctypes.data, C.POINTER(RdsStats)))
+
+    @property
+    def pi(self):
+        return int(self.s.pi) if self.s.pi_valid else None
+
+    @property
+    def ps(self):
+        return bytes(self.s.ps_done).decode("latin-1") if self.s.ps_complete else None
+
+    @property
+    def af_mhz(self):
+        return [self.s.af[i] / 10.0 for i in range(min(self.s.af_n, 25))]
+
+    def bler(self) -> float:
+        return float(lib().sdr_rds_station_bler(C.byref(self.s)))
+
+    def text(self) -> str:
+        buf = C.create_string_buffer(2048)
+        lib().sdr_rds_station_format(C.byref(self.s), buf, len(buf))
+        return buf.value.decode("ascii", errors="replace")
 
 
 # ------------------------------------------------------------------ batched primitives (torch tensors)

@@ -2,7 +2,7 @@
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
 //   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
-//             [--deemph US] [--blend] [--demod ref|phase]
+//             [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N]]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //   sdr_multi NCH --wide W [--shift S] --tune FILE ...          (the receiver on wide captures)
 //   sdr_multi NWIDE --wide W [--shift S] --scan ...             (the scan of wide captures)
@@ -36,6 +36,11 @@
 // --demod phase: the phase discriminator (SDR_FLAG_PHASE_DEMOD, include/sdr_amd.h) instead of the
 // reference's (--demod ref, the default): the audio of a loud station no longer folds, and with --meter every
 // PREFIX.status line also ends with the run's peak deviation and mean offset in kHz. Not with --fast.
+// --rds-decode: the RDS group decoder (include/sdr_amd.h, sdr_rds_*; mode 0) behind the RDS thread's bits --
+// PREFIX.groups, one line per group ("ch <c> bits <n> AAAA BBBB CCCC DDDD", "----" for a block that was not
+// received, a trailing "*" on a corrected one), and PREFIX.radio, per channel PI, PTY, TP/TA/MS, PS, RadioText,
+// clock time, AF, the groups by type, block counts, BLER, slips and syncs; --rds-correct N (0-5, default 2):
+// the longest error burst it corrects. Every other file is that of a run without it.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +51,7 @@
 #include "sdr_multi.h"
 #include "sdr_multi_audio.h"
 #include "sdr_multi_meter.h"
+#include "sdr_multi_rds.h"
 #include "sdr_multi_tuned.h"
 #include "sdr_multi_wide.h"
 #include "sdr_scan_run.h"
@@ -54,7 +60,7 @@
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
-                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase]\n"
+                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N]]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
                          "       sdr_multi NCH --wide W [--shift S] --tune FILE ...   |   sdr_multi NWIDE --wide W [--shift S] --scan ...\n"
@@ -64,6 +70,8 @@ namespace {
                          "  --blend: PREFIX.audio blended to mono where the meter finds no pilot (needs --meter)\n"
                          "  --demod phase: the phase discriminator (fm_demod in radians, no fold above if_Fs/4 of deviation;\n"
                          "            PREFIX.status gains peak_khz and offset_khz); ref (default): the reference's; not with --fast\n"
+                         "  --rds-decode: also write PREFIX.groups (one line per RDS group) and PREFIX.radio (PI, PS, RadioText,\n"
+                         "            clock time, AF, block error rate per channel); --rds-correct N: bursts up to N bits (0-5, default 2)\n"
                          "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n"
                          "  --wide W: the input is wide int8 I/Q at W (4, 8, 10) times rf_Fs, rows of 2*W*block_iq bytes, each\n"
                          "            split into 2W-1 capture rows (--shift S: output shift 1-24); needs --tune or --scan\n");
@@ -78,7 +86,9 @@ int main(int argc, char** argv) {
     o.pll_cus = 64;
     std::string in = "-", out = "sdr_multi", tune_path;
     if (o.nch <= 0) usage();
-    bool scan = false, meter = false, blend = false, finish = false;
+    bool scan = false, meter = false, blend = false, finish = false, rds_decode = false, rds_correct = false;
+    sdr_rds_opts ro{};
+    sdr_rds_opts_default(&ro);
     int wide_w = 0, wide_shift = 0;
     sdr_audio_opts ao{};
     sdr_audio_opts_default(&ao);
@@ -111,6 +121,13 @@ int main(int argc, char** argv) {
         else if (a == "--scan-blocks" && i + 1 < argc) so.max_blocks = std::atoi(argv[++i]);
         else if (a == "--step" && i + 1 < argc) so.pick.step_khz = std::atoi(argv[++i]);
         else if (a == "--thr" && i + 1 < argc) so.pick.thr_db = (float)std::atof(argv[++i]);
+        else if (a == "--rds-decode") rds_decode = true;
+        else if (a == "--rds-correct" && i + 1 < argc) {
+            const std::string n = argv[++i];
+            if (n.size() != 1 || n[0] < '0' || n[0] > '5') usage();
+            ro.max_burst = n[0] - '0';
+            rds_correct = true;
+        }
         else if (a == "--fast") o.flags |= SDR_FLAG_FAST_FRONTEND;
         else if (a == "--demod" && i + 1 < argc) {
             const std::string d = argv[++i];
@@ -125,6 +142,8 @@ int main(int argc, char** argv) {
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();
     if (blend && !meter) usage();
+    if (rds_correct && !rds_decode) usage();
+    if (rds_decode && (scan || !sdr_rds_mode_ok(o.mode))) usage();   // a scan demodulates nothing; modes 1-3 have no RDS bit clock
     if (wide_shift && !wide_w) usage();
     if (wide_w && !scan && tune_path.empty()) usage();        // a wide run is always tuned
     if (scan && wide_w) {
@@ -207,7 +226,10 @@ int main(int argc, char** argv) {
     sdr_meter_opts mo{};
     sdr_meter_opts_default(&mo);
     const sdr_multi_tuning* tp = tune_path.empty() ? nullptr : &tune;
-    const int rc = wide_w  ? sdr_multi_run_wide(&o, &wd, tp, meter ? &mo : nullptr, finish ? &ao : nullptr, blend ? 1 : 0, &st)
+    const sdr_multi_rds rd{ro.max_burst, ro.loss_blocks};
+    const int rc = rds_decode ? sdr_multi_run_rds(&o, wide_w ? &wd : nullptr, tp, meter ? &mo : nullptr, finish ? &ao : nullptr,
+                                                  blend ? 1 : 0, &rd, &st)
+                   : wide_w ? sdr_multi_run_wide(&o, &wd, tp, meter ? &mo : nullptr, finish ? &ao : nullptr, blend ? 1 : 0, &st)
                    : finish ? sdr_multi_run_finished(&o, tp, meter ? &mo : nullptr, &ao, blend ? 1 : 0, &st)
                    : meter ? sdr_multi_run_metered(&o, tp, &mo, &st)
                            : sdr_multi_run_tuned(&o, tp, &st);

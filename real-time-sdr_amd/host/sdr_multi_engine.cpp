@@ -23,6 +23,10 @@
 // A finished run (include/sdr_multi_audio.h) adds, behind them on the audio thread's post stream,
 // sdr_audio_blend_from_meter (with --blend) and sdr_audio_finish from the block's L/R rows into rows of
 // its own, copied out behind the L/R copy and written to PREFIX.audio.
+// A decoding run (include/sdr_multi_rds.h) adds sdr_rds_groups behind the RDS thread's sdr_rds_bits, on the
+// device rows those bits are in; the block's group records are copied out with the bits, the frame layer
+// appends them to PREFIX.groups and feeds one sdr_rds_station per channel, and PREFIX.radio is written at
+// the end from the stations and the decoder's counters.
 // Streams (the four-queue budget of DESIGN.md 5): the producer's front end and both consumers' pre
 // parts share one stream (s_fe), both consumers' post parts another (s_post), and each consumer's
 // PLL has its own CU-masked stream -- with a known block count ONE persistent launch per consumer
@@ -74,6 +78,7 @@
 #include "sdr_multi.h"
 #include "sdr_multi_audio.h"
 #include "sdr_multi_meter.h"
+#include "sdr_multi_rds.h"
 #include "sdr_multi_tuned.h"
 #include "sdr_multi_wide.h"
 
@@ -92,6 +97,7 @@ struct RunSpec {
     const sdr_audio_opts* audio = nullptr;    // audio finishing (sdr_multi_run_finished)
     bool blend = false;                       //   its blend targets follow the meter's rows
     const sdr_multi_wide* wide = nullptr;     // wide captures (sdr_multi_run_wide)
+    const sdr_multi_rds* rds = nullptr;       // the RDS group decoder (sdr_multi_run_rds)
 };
 
 // Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused.
@@ -104,6 +110,9 @@ bool validate(const RunSpec& r) {
         if (sdr_audio_coeffs(o->mode, r.audio->tau_us, &a, &b) != SDR_OK || !(r.audio->blend_hi > r.audio->blend_lo)) return false;
     }
     if (o->nch <= 0 || (!o->in_path && (!o->d_iq || o->nblocks <= 0))) return false;
+    if (const sdr_multi_rds* d = r.rds)   // what sdr_rds_dec_create would refuse, and a mode without an RDS bit clock
+        if (d->max_burst < 0 || d->max_burst > 5 || d->loss_blocks < 1 || d->loss_blocks > 64 || !sdr_rds_mode_ok(o->mode))
+            return false;
     if (const sdr_multi_tuning* t = r.tune) {   // the tuning's bounds (sdr_tuner_set's)
         int N = 0;
         if (sdr_tuner_table(o->mode, nullptr, 0, &N) != SDR_OK) return false;
@@ -385,7 +394,12 @@ struct RdsRes {
     DevBuf<uint8_t> d_bits;
     Pinned<int32_t> h_nbits[NH];
     Pinned<uint8_t> h_bits[NH];
-    RdsRes(int nch, bool cache) {
+    // a decoding run (sdr_multi_run_rds): the group decoder and the pinned copies of a block's records
+    sdr_rds_dec* dec = nullptr;
+    Pinned<sdr_rds_group> h_groups[NH];
+    Pinned<int32_t> h_ngroups[NH];
+    RdsRes(const sdr_multi_opts& o, const sdr_multi_rds* rds, bool cache) {
+        const int nch = o.nch;
         pre.make();
         pll.make();
         d_nbits.get((size_t)nch);
@@ -395,6 +409,16 @@ struct RdsRes {
             h_nbits[h].take(nch * sizeof(int32_t), cache);
             h_bits[h].take((size_t)nch * SDR_MAX_BITS, cache);
         }
+        if (!rds) return;
+        const sdr_rds_opts ro{rds->max_burst, rds->loss_blocks};
+        check_sdr(sdr_rds_dec_create(&dec, o.device, nch, &ro), "sdr_rds_dec_create");
+        for (int h = 0; h < NH; h++) {
+            h_groups[h].take((size_t)nch * SDR_RDS_MAX_GROUPS * sizeof(sdr_rds_group), cache);
+            h_ngroups[h].take(nch * sizeof(int32_t), cache);
+        }
+    }
+    ~RdsRes() {
+        if (dec) (void)sdr_rds_dec_destroy(dec);
     }
 };
 
@@ -857,6 +881,11 @@ void rds_thread(Shared* sh) {
     RdsRes& r = *sh->rr;
     MeterOut* mt = sh->meter ? &*sh->meter : nullptr;
     std::vector<FrameState> fs((size_t)o.nch);
+    // a decoding run: every channel's station, and PREFIX.groups as the blocks come in
+    std::vector<sdr_rds_station> stations(r.dec ? (size_t)o.nch : 0);
+    for (auto& st : stations) sdr_rds_station_init(&st);
+    File groups;
+    if (r.dec && o.out_prefix) groups.open(std::string(o.out_prefix) + ".groups", "w");
     auto enqueue = [&](long long b) {
         const int k = (int)(b % NH);
         check_sdr(sdr_rds_pre(ctx, fe_stream(sh, b)), "sdr_rds_pre");
@@ -870,6 +899,10 @@ void rds_thread(Shared* sh) {
         check_sdr(sdr_rds_bits(ctx, nullptr, nullptr, nullptr, 0, r.d_nbits.p, r.d_bits.p, SDR_MAX_BITS, s), "sdr_rds_bits");
         check_hip(hipMemcpyAsync(r.h_nbits[k], r.d_nbits.p, o.nch * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
         check_hip(hipMemcpyAsync(r.h_bits[k], r.d_bits.p, (size_t)o.nch * SDR_MAX_BITS, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+        if (r.dec) {   // on the bits where they are; the last block's stream follows the others' (consumer_pll)
+            check_sdr(sdr_rds_groups(r.dec, r.d_nbits.p, r.d_bits.p, SDR_MAX_BITS, s), "sdr_rds_groups");
+            check_sdr(sdr_rds_groups_copy(r.dec, r.h_groups[k], r.h_ngroups[k], s), "sdr_rds_groups_copy");
+        }
         check_hip(hipEventRecord(r.out_ready[k], s), "hipEventRecord");
     };
     auto frame_layer = [&](long long blk) {   // rds.cpp:181-189 per channel; parse() prints to cerr
@@ -883,6 +916,21 @@ void rds_thread(Shared* sh) {
                 o.cap_nbits[(size_t)blk * o.ncap + i] = h_nbits[o.cap_ch[i]];
                 std::memcpy(o.cap_bits + ((size_t)blk * o.ncap + i) * SDR_MAX_BITS, h_bits + (size_t)o.cap_ch[i] * SDR_MAX_BITS,
                             SDR_MAX_BITS);
+            }
+        if (r.dec)
+            for (int c = 0; c < o.nch; c++) {
+                const int ng = std::min(std::max(r.h_ngroups[k][c], 0), SDR_RDS_MAX_GROUPS);
+                for (int j = 0; j < ng; j++) {
+                    const sdr_rds_group& g = r.h_groups[k][(size_t)c * SDR_RDS_MAX_GROUPS + j];
+                    sdr_rds_station_update(&stations[(size_t)c], &g);
+                    if (!groups) continue;
+                    std::fprintf(groups, "ch %d bits %u", c, g.bits);
+                    for (int w = 0; w < 4; w++) {
+                        if (!((g.ok >> w) & 1)) std::fprintf(groups, " ----");
+                        else std::fprintf(groups, " %04X%s", g.w[w], ((g.corrected >> w) & 1) ? "*" : "");
+                    }
+                    std::fprintf(groups, "\n");
+                }
             }
         if (!o.out_prefix) return;
         std::streambuf* saved = std::cerr.rdbuf();
@@ -908,6 +956,19 @@ void rds_thread(Shared* sh) {
     };
     consumer_loop(sh, ctx, 1, enqueue, frame_layer);
     if (!o.out_prefix) return;
+    if (r.dec) {   // PREFIX.radio: what every station said, and how well it was received
+        std::vector<sdr_rds_stats> stats((size_t)o.nch);
+        check_sdr(sdr_rds_stats_read(r.dec, stats.data(), sh->s_post_c[1]), "sdr_rds_stats_read");
+        File radio;
+        radio.open(std::string(o.out_prefix) + ".radio", "w");
+        std::vector<char> buf(4096);
+        for (int c = 0; c < o.nch; c++) {
+            sdr_rds_station_stats(&stations[(size_t)c], &stats[(size_t)c]);
+            sdr_rds_station_format(&stations[(size_t)c], buf.data(), buf.size());
+            std::istringstream lines(buf.data());
+            for (std::string line; std::getline(lines, line);) std::fprintf(radio, "ch %d: %s\n", c, line.c_str());
+        }
+    }
     File f;
     f.open(std::string(o.out_prefix) + ".rds", "w");
     for (int c = 0; c < o.nch; c++) {
@@ -996,7 +1057,7 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     mark("streams");
     const size_t lr_bytes = 2 * (size_t)sh.info.n_audio * o.nch * sizeof(int16_t);
     sh.ar.emplace(lr_bytes, sw.pin_cache);
-    sh.rr.emplace(o.nch, sw.pin_cache);
+    sh.rr.emplace(o, spec.rds, sw.pin_cache);
     if (spec.meter) sh.meter.emplace(o, *spec.meter, sw.pin_cache);
     if (spec.audio) sh.fin.emplace(o, *spec.audio, spec.blend, lr_bytes, sw.pin_cache);
     mark("consumer buffers");
@@ -1089,4 +1150,12 @@ extern "C" int sdr_multi_run_wide(const sdr_multi_opts* opts, const sdr_multi_wi
     if (!wide) return sdr_multi_run_finished(opts, tune, mo, ao, blend, stats);
     if (!tune) return SDR_E_INVALID;
     return multi_run({opts, tune, mo, ao, blend != 0, wide}, stats);
+}
+
+extern "C" int sdr_multi_run_rds(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
+                                 const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, const sdr_multi_rds* rds,
+                                 sdr_multi_stats* stats) {
+    if (!rds) return sdr_multi_run_wide(opts, wide, tune, mo, ao, blend, stats);
+    if (wide && !tune) return SDR_E_INVALID;
+    return multi_run({opts, tune, mo, ao, blend != 0, wide, rds}, stats);
 }
