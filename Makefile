@@ -12,11 +12,13 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-g
             -mllvm -pragma-unroll-threshold=1000000 \
             -Wall -Iinclude
 LIB      := $(PKG)/libsdr_amd.so
-SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_scan.hip \
+SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_ctx.hip $(PKG)/csrc/sdr_plls.cpp $(PKG)/csrc/sdr_streams.hip \
+            $(PKG)/csrc/sdr_primitives.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_scan.hip \
             $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip $(PKG)/csrc/sdr_split.hip \
             $(PKG)/csrc/sdr_rds.hip $(PKG)/csrc/sdr_taps.cpp $(PKG)/csrc/sdr_rds_text.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
-HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h $(PKG)/csrc/demod_phase.h
+HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h $(PKG)/csrc/demod_phase.h \
+            $(PKG)/csrc/nco.h $(PKG)/csrc/stage_device.h
 
 # host C++ (no device code): compiled by the system g++ against the HIP runtime headers
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include \
@@ -41,6 +43,8 @@ host: $(HOSTLIB) $(CLI) $(MULTI)
 # the lane-pair PLL step is faster scalar too (packed-f32 results cost a wait state on gfx950,
 # profiles/r03/ab_pll_split3.txt)
 build/sdr_kernels.hip.o: HIPFLAGS += -fno-slp-vectorize
+# the units split off sdr_kernels.hip keep its flags for the kernels they took along
+build/sdr_ctx.hip.o build/sdr_streams.hip.o build/sdr_primitives.hip.o: HIPFLAGS += -fno-slp-vectorize
 # the band scan's complex multiply-adds are four scalar v_fma_f32 with SGPR twiddles: no SLP either
 build/sdr_scan.hip.o: HIPFLAGS += -fno-slp-vectorize
 # the meter's noise FIR keeps its multiplies and adds scalar and in tap order: no SLP

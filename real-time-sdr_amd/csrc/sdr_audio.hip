@@ -24,14 +24,6 @@
 
 #pragma clang fp contract(off)
 
-// sdr_meter.hip's handle, restated token for token (its nch, mode and device have no accessor in the
-// C ABI and sdr_audio_blend_from_meter must refuse a meter of another shape): keep the two alike
-struct sdr_meter {
-    int device = 0, nch = 0, mode = 0;
-    float* h = nullptr;             // the noise band-pass taps (device)
-    sdr_meter_row* rows = nullptr;  // [nch] (device)
-};
-
 struct sdr_audio {
     int device = 0, nch = 0, mode = 0, width = 0, n = 0, block_if = 0, shape = 0;
     float a = 0.0f, b = 1.0f, lo = 0.0f, hi = 0.0f;

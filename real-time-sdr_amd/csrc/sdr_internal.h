@@ -2,7 +2,12 @@
 //
 //   sdr_frontend.hip   u8 I/Q -> 101-tap FIR /D on I and Q -> discriminator   rffrontend.cpp:58-71
 //   sdr_pll.hip        PLL / NCO recurrences, persistent PLL hand-offs        pll.cpp:4-61
-//   sdr_kernels.hip    IF FIRs, resamplers, mixers, RDS bits, context and the C ABI
+//   sdr_kernels.hip    IF FIRs, resamplers, mixers, RDS bits: the stage kernels and the stage calls
+//   sdr_ctx.hip        context lifecycle (mode table, buffers, tap tables), last error, parity release
+//   sdr_plls.cpp       host protocol of the persistent PLL launch (prepare, launch, signal, wait, report)
+//   sdr_streams.hip    CU-masked streams and their placement, per-stream scratch, sdr_hbm_copy, test hooks
+//   sdr_primitives.hip the context-free primitives (FIR, resampler, demod, fmpll, cdr, bit decoders)
+//   stage_device.h     device code shared by sdr_kernels.hip and sdr_primitives.hip
 //   sdr_scan.hip       band scan of the capture rows
 //   sdr_meter.hip      reception meter: per-channel readings of a block's rows
 //   sdr_split.hip      wideband splitter: a wide s8 capture into the capture rows (its own handle)
@@ -17,6 +22,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <mutex>
 #include <vector>
 
 #include "sdr_amd.h"
@@ -153,7 +159,7 @@ struct CuPlacement {
     int min_units = 0;      // min over active XCCs of (active SEs x min CUs per active SE)
     long long resident(int per_cu) const { return (long long)xcc_active * min_units * per_cu; }
 };
-CuPlacement cu_placement(const uint32_t* mask, int nwords, int ncu_dev, int nxcc);
+CuPlacement cu_placement(const uint32_t* mask, int nwords, int ncu_dev, int nxcc);   // (sdr_streams.hip)
 // the persistent PLL launch's shape for jobs.p[k].j[0 .. njobs) (njobs = 2: the stereo and RDS PLLs,
 // 1: one of them): kernel, workgroups, waves, and how many of its workgroups the placement keeps
 // resident at once (resident < groups: the launch would hang)
@@ -184,18 +190,68 @@ constexpr uint32_t PLL_SUB_SCALE = 8;
 constexpr uint32_t PLL_DONE_RING = 16; // waves stay within a few blocks of each other
 constexpr int PLL_WORDS = PLL_WORDS_DONE + (int)PLL_DONE_RING;
 
-// ---- sdr_kernels.hip, for sdr_meter.hip
+inline hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
+
+// ---- sdr_kernels.hip
+constexpr int FRB_R = 8;                   // outputs per thread of the register-blocked 101-tap FIRs (k_fir_rb)
+constexpr int FRB_TILE = BLK * FRB_R;      // outputs per workgroup (the parts of sdr_frontend_pre_parts)
+
+// ---- sdr_ctx.hip
 int mode_info(sdr_info* in, int nch, int mode, int rds_on);   // the mode table (sdr_ctx_info of such a context)
-int ctx_check_failed(const sdr_ctx* c, const char* what);     // SDR_E_TIMEOUT after a release timeout
-// the meter read the current block's parity buffers on s: part 0 fm and pilot (sdr_meter_audio),
-// part 1 rds_band (sdr_meter_rds); records the release (sdr_ctx rel_words)
-int meter_release(sdr_ctx* c, int part, hipStream_t s);
+// polyphase tap table: row p holds h[p], h[p+U], ... (cnt[p] entries), rows padded to L
+struct Polyphase {
+    std::vector<float> table;
+    std::vector<int> cnt;
+    int L = 0;
+};
+Polyphase make_polyphase(const std::vector<float>& h, int U);
+// the front end's arguments for the block that switches the context to parity p
+FrontendArgs frontend_args(const sdr_ctx* c, const uint8_t* iq, size_t iq_stride, int p);
+PllJob stereo_job(sdr_ctx* c);   // stereo.cpp:77: fmpll(pilot, 19e3, rf_Fs/rf_decim, ..., 2.0, 0, 0.01)
+PllJob rds_job(sdr_ctx* c);      // rds.cpp:119: fmpll(gen_pilot, 114e3, if_Fs, ..., 0.5, 0, 0.001)
+// parity release (sdr_ctx::Rel): the slots' readers, as bits of a wait's slot set
+constexpr unsigned REL_MONO = 1u, REL_STEREO = 2u, REL_RDS = 4u, REL_METER_A = 8u, REL_METER_R = 16u;
+constexpr unsigned REL_ALL = REL_MONO | REL_STEREO | REL_RDS | REL_METER_A | REL_METER_R;
+// the reader `slot` (one REL_ bit) has read the current block's parity buffers on s
+int release_record(sdr_ctx* c, unsigned slot, hipStream_t s);
+// s waits until the readers `slots` of parity p have released the last block they read
+int release_wait(sdr_ctx* c, int p, unsigned slots, hipStream_t s);
+int check_failed(const sdr_ctx* c, const char* what);         // SDR_E_TIMEOUT after a release timeout
+
+// ---- sdr_plls.cpp
+// a persistent launch the host already knows timed out (sdr_plls_report): its blocks' post stages fail
+int check_pers_failed(const sdr_ctx* c, const char* what);
+// after a stage that read the persistent launch's error word was enqueued on s
+int pers_reader_mark(sdr_ctx* c, hipStream_t s);
+// sdr_frontend_pre_parts: may the next block come in parts (the first block of a launch of both PLLs)?
+int plls_parts_check(const sdr_ctx* c, const char* what);
+// ... and its FIR tiles [0, tiles) are published on s
+int plls_parts_publish(sdr_ctx* c, int tiles, hipStream_t s);
+
+// ---- sdr_streams.hip
+// a stream made by sdr_stream_create_cu_range: its device and (place non-null) its CU placement
+bool masked_stream(hipStream_t s, int* device, CuPlacement* place);
+// the mask of CUs [first_cu, first_cu + n_cu) of a device (or of every other CU: exclude)
+std::vector<uint32_t> cu_range_mask(int ncu, int first_cu, int n_cu, int exclude, int* nset);
+int device_xccs(int device);
+// one scratch buffer per (device, stream), grown on demand; the caller holds g_scratch_mu until its
+// kernels using the buffer are enqueued, so that another host thread on the same stream cannot grow
+// (free) the buffer in between
+extern std::mutex g_scratch_mu;
+int stream_scratch(hipStream_t s, size_t bytes, void** out);
 
 }  // namespace sdrk
 
 // ============================================================================================
-// Context (sdr_kernels.hip owns it; the other units see the layout)
+// Handles shared by units (sdr_ctx.hip owns the context, sdr_meter.hip the meter; the other units
+// see the layouts)
 // ============================================================================================
+struct sdr_meter {
+    int device = 0, nch = 0, mode = 0;
+    float* h = nullptr;             // the noise band-pass taps (device)
+    sdr_meter_row* rows = nullptr;  // [nch] (device)
+};
+
 struct sdr_ctx {
     int device = 0, nch = 0, mode = 0, rds_on = 0, flags = 0;
     sdr_info info{};
@@ -242,58 +298,68 @@ struct sdr_ctx {
     long long st_pre_done = -1, st_pll_done = -1, rds_pre_done = -1, rds_pll_done = -1;
     // persistent PLLs (sdr_plls_launch / _signal / _wait): device words (launch_pll_multi), per-block
     // timestamps of the last launch, and the host's sequence bookkeeping
-    uint32_t* pers_words = nullptr;
-    unsigned long long *pers_t0 = nullptr, *pers_t1 = nullptr;
-    unsigned long long* pers_cyc = nullptr;             // [block][2]: sums over waves of cycles, 100 MHz ticks
-    int pers_tcap = 0, pers_last_n = 0;
-    int pers_prepared = 0;                              // sdr_plls_prepare's nblocks (0: none pending)
-    uint32_t pers_prepared_launch = 0;                  // pers_launched when it was prepared
-    uint32_t pers_launched = 0, pers_signaled = 0, pers_waves = 0;
-    int pers_which = SDR_PLLS_BOTH;                     // the PLLs the last launch runs (sdr_plls_launch_sel)
-    uint32_t pers_base = 0;                             // sequence number of the last launch's first block
-    uint32_t pers_waited = 0;                           // sequence numbers below this have been waited for
-    long long pers_first_block = -1;                    // the context block that sequence number belongs to
-    hipStream_t pers_stream = nullptr;                  // stream of the last launch
-    long long pers_block = -1;                          // block of the last signal
-    uint32_t pers_block_seq = 0;                        // its sequence number
-    hipEvent_t pers_ev = nullptr;                       // orders a prepare on another stream after the last launch
-    // parity release (sdr_kernels.hip release_record / release_wait): rel_words[p][slot] counts the
+    // Only sdr_plls.cpp touches it (the post stages through block_poison, check_pers_failed and
+    // pers_reader_mark; sdr_ctx.hip frees its events and forgets the launch in sdr_ctx_reset).
+    struct Pers {
+        uint32_t* words = nullptr;
+        unsigned long long *t0 = nullptr, *t1 = nullptr;
+        unsigned long long* cyc = nullptr;              // [block][2]: sums over waves of cycles, 100 MHz ticks
+        int tcap = 0, last_n = 0;
+        int prepared = 0;                               // sdr_plls_prepare's nblocks (0: none pending)
+        uint32_t prepared_launch = 0;                   // launched when it was prepared
+        uint32_t launched = 0, signaled = 0, waves = 0;
+        int which = SDR_PLLS_BOTH;                      // the PLLs the last launch runs (sdr_plls_launch_sel)
+        uint32_t base = 0;                              // sequence number of the last launch's first block
+        uint32_t waited = 0;                            // sequence numbers below this have been waited for
+        long long first_block = -1;                     // the context block that sequence number belongs to
+        hipStream_t stream = nullptr;                   // stream of the last launch
+        long long block = -1;                           // block of the last signal
+        uint32_t block_seq = 0;                         // its sequence number
+        hipEvent_t ev = nullptr;                        // orders a prepare on another stream after the last launch
+        bool failed = false;                            // sdr_plls_report saw a timeout of the current launch
+        // streams whose post stages read the last launch's error word (sdr_plls_wait): the next launch's
+        // prepare clears that word only after them (events recorded on each, waited for on its stream)
+        static constexpr int READERS = 4;
+        hipStream_t readers[READERS] = {};
+        int nreaders = 0;
+        hipEvent_t reader_ev[READERS] = {};
+        // the persistent launch's error word the post stages of the current block check (their outputs
+        // are poisoned when a persistent wait timed out): only for blocks signalled through a launch
+        const uint32_t* err(long long cur_block) const { return (words && block == cur_block) ? words + 1 : nullptr; }
+    } pers;
+    // parity release (sdr_ctx.hip release_record / release_wait): words[p][slot] counts the
     // blocks of parity p read by slot 0 sdr_mono (fm), 1 sdr_stereo_post (fm, band, t_st, carrier),
-    // 2 sdr_rds_post's mixer (rband, t_rds, ipll), stored on the reader's stream (rel_stream) after
+    // 2 sdr_rds_post's mixer (rband, t_rds, ipll), stored on the reader's stream (stream) after
     // its kernels; the producers of the block two later wait for the count on their own streams.
     // Slots 3 and 4 are the reception meter's two calls (sdr_meter.hip), which may run on two streams:
     // 3 sdr_meter_audio (fm, pilot), 4 sdr_meter_rds (rband); their counts stay 0, and nothing waits
     // for them, on a context no meter call ran on
-    static constexpr int REL_SLOTS = 5;
-    uint32_t* rel_words = nullptr;                      // [2][REL_SLOTS] counters
-    uint32_t rel_seq[2][REL_SLOTS] = {};
-    hipStream_t rel_stream[2][REL_SLOTS] = {};
-    uint32_t rel_waited[2][REL_SLOTS] = {};            // the count a wait on rel_waited_on already covers
-    hipStream_t rel_waited_on[2][REL_SLOTS] = {};
-    bool pers_failed = false;                           // sdr_plls_report saw a timeout of the current launch
-    // streams whose post stages read the last launch's error word (sdr_plls_wait): the next launch's
-    // prepare clears that word only after them (events recorded on each, waited for on its stream)
-    static constexpr int PERS_READERS = 4;
-    hipStream_t pers_readers[PERS_READERS] = {};
-    int pers_nreaders = 0;
-    hipEvent_t pers_reader_ev[PERS_READERS] = {};
-    // the persistent launch's error word the post stages of the current block check (their outputs
-    // are poisoned when a persistent wait timed out): only for blocks signalled through a launch
-    const uint32_t* pers_err() const { return (pers_words && pers_block == block) ? pers_words + 1 : nullptr; }
-    // release timeout (sdr_kernels.hip release_wait): fail_words[0] is set on the device by a parity
-    // release wait that gave up (a reader had not released a buffer within ~5 s, and the producer
-    // then overwrote it); every output stage poisons its block while it is set, and the same wait sets
-    // the host-mapped *fail_host, which every later stage call checks (SDR_E_TIMEOUT). sdr_ctx_reset
-    // clears both.
-    uint32_t* fail_words = nullptr;
-    uint32_t* fail_host = nullptr;                      // hipHostMalloc'd (coherent), host view
-    uint32_t* fail_host_dev = nullptr;                  // its device address
-    // sdr_frontend_timing: the dispatch stamps of the next fe_time_cap whole-block front-end launches
-    std::vector<hipEvent_t> fe_ev;                      // [2 * cap]: start, end per launch (HIP events)
-    unsigned long long* fe_stamps = nullptr;            // [cap][fe_stamp_wgs][2] (k_frontend2's own stamps)
-    int fe_stamp_wgs = 0, fe_stamp_cap = 0;
-    bool fe_use_stamps = false;                         // the exact front end (k_frontend2): stamps
-    int fe_time_cap = 0, fe_time_n = 0;
+    // The release functions of sdr_ctx.hip own it; the output stages read fail_words (block_poison).
+    struct Rel {
+        static constexpr int SLOTS = 5;
+        uint32_t* words = nullptr;                      // [2][SLOTS] counters
+        uint32_t seq[2][SLOTS] = {};
+        hipStream_t stream[2][SLOTS] = {};
+        uint32_t waited[2][SLOTS] = {};                 // the count a wait on waited_on already covers
+        hipStream_t waited_on[2][SLOTS] = {};
+        // release timeout (sdr_ctx.hip release_wait): fail_words[0] is set on the device by a parity
+        // release wait that gave up (a reader had not released a buffer within ~5 s, and the producer
+        // then overwrote it); every output stage poisons its block while it is set, and the same wait sets
+        // the host-mapped *fail_host, which every later stage call checks (SDR_E_TIMEOUT). sdr_ctx_reset
+        // clears both.
+        uint32_t* fail_words = nullptr;
+        uint32_t* fail_host = nullptr;                  // hipHostMalloc'd (coherent), host view
+        uint32_t* fail_host_dev = nullptr;              // its device address
+    } rel;
+    // sdr_frontend_timing: the dispatch stamps of the next cap whole-block front-end launches
+    // The sdr_frontend_timing family of sdr_kernels.hip owns it (sdr_ctx.hip frees it).
+    struct FeTime {
+        std::vector<hipEvent_t> ev;                     // [2 * cap]: start, end per launch (HIP events)
+        unsigned long long* stamps = nullptr;           // [stamp_cap][stamp_wgs][2] (k_frontend2's own stamps)
+        int stamp_wgs = 0, stamp_cap = 0;
+        bool use_stamps = false;                        // the exact front end (k_frontend2): stamps
+        int cap = 0, n = 0;
+    } fe_time;
     std::vector<void*> allocs;
 
     float* fm_cur() const { return fm + parity * fm_par; }

@@ -27,12 +27,6 @@
 
 #pragma clang fp contract(off)
 
-struct sdr_meter {
-    int device = 0, nch = 0, mode = 0;
-    float* h = nullptr;             // the noise band-pass taps (device)
-    sdr_meter_row* rows = nullptr;  // [nch] (device)
-};
-
 namespace sdrk {
 namespace {
 
@@ -369,7 +363,7 @@ int sdr_meter_reset(sdr_meter* m, void* stream) {
 // the checks both calls share: handles, the context's state, the same shape and device
 static int meter_check(const sdr_meter* m, const sdr_ctx* c, const char* what) {
     if (!m || !c) return fail(SDR_E_INVALID, "%s: null handle", what);
-    if (const int rf = ctx_check_failed(c, what)) return rf;
+    if (const int rf = check_failed(c, what)) return rf;
     if (c->nch != m->nch || c->mode != m->mode || c->device != m->device)
         return fail(SDR_E_INVALID, "%s: the context (nch %d, mode %d, device %d) is not the meter's (%d, %d, %d)", what,
                     c->nch, c->mode, c->device, m->nch, m->mode, m->device);
@@ -398,7 +392,7 @@ int sdr_meter_audio(sdr_meter* m, sdr_ctx* c, const int16_t* lr, size_t lr_strid
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_meter_audio, dim3(m->nch), dim3(MT), (size_t)(NOISE_H + in.block_if) * sizeof(float), s, a);
     LAUNCH_CHECK();
-    return meter_release(c, 0, s);   // fm and pilot of this parity read
+    return release_record(c, REL_METER_A, s);   // fm and pilot of this parity read
 }
 
 int sdr_meter_rds(sdr_meter* m, sdr_ctx* c, void* stream) {
@@ -420,7 +414,7 @@ int sdr_meter_rds(sdr_meter* m, sdr_ctx* c, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_meter_rds, dim3(m->nch), dim3(MT), (size_t)in.n_rds * sizeof(float), s, a);
     LAUNCH_CHECK();
-    return meter_release(c, 1, s);   // rds_band of this parity read
+    return release_record(c, REL_METER_R, s);   // rds_band of this parity read
 }
 
 int sdr_meter_read(sdr_meter* m, sdr_meter_row* host_rows, void* stream) {

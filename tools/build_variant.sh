@@ -9,11 +9,11 @@ d=build/variants/$name.obj
 mkdir -p $d
 common="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-gpu-flush-denormals-to-zero -mllvm -pragma-unroll-threshold=1000000 -Iinclude"
 pids=""
-for f in sdr_kernels.hip sdr_frontend.hip sdr_pll.hip sdr_scan.hip sdr_meter.hip sdr_audio.hip sdr_split.hip sdr_taps.cpp; do
+for f in sdr_kernels.hip sdr_ctx.hip sdr_plls.cpp sdr_streams.hip sdr_primitives.hip sdr_frontend.hip sdr_pll.hip sdr_scan.hip sdr_meter.hip sdr_audio.hip sdr_split.hip sdr_rds.hip sdr_taps.cpp sdr_rds_text.cpp; do
   extra=""
   case $f in
     sdr_kernels.hip) extra="-fno-slp-vectorize ${KFLAGS:-}";;
-    sdr_scan.hip|sdr_meter.hip|sdr_audio.hip) extra="-fno-slp-vectorize";;
+    sdr_ctx.hip|sdr_streams.hip|sdr_primitives.hip|sdr_scan.hip|sdr_meter.hip|sdr_audio.hip) extra="-fno-slp-vectorize";;
     sdr_frontend.hip) extra="${FEFLAGS:-}";;
     sdr_pll.hip) extra="-fno-slp-vectorize ${PLLFLAGS--mllvm -amdgpu-sched-strategy=max-ilp}";;
   esac
