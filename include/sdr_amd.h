@@ -561,6 +561,70 @@ const char *sdr_rds_pty_name(int pty);
 /* a multi-line report into buf (always terminated when n > 0); returns the length it needs */
 size_t sdr_rds_station_format(const sdr_rds_station *s, char *buf, size_t n);
 
+/* ---- RDS symbol tracker (no reference counterpart; sdr_version stays 3, callers detect it by symbol): a
+ * bit clock that runs on from call to call and a biphase correlator over the whole bit, in place of the
+ * per-block cdr() and one-sample slicer of sdr_rds_bits. It reads rds_clean rows ([nch][stride] f32, n
+ * samples a call, as sdr_rds_dsp hands them out) and writes nbits [nch] and bits [nch][bits_stride], 0/1
+ * bytes, differentially decoded, in sdr_rds_bits' layout: sdr_rds_groups takes them unchanged. Mode 0 only
+ * (sdr_rds_mode_ok): S = symbol_Fs = 39 samples a chip, B = 2 S = 78 a bit. One quantisation, then all
+ * integer; tests/rds_track_model.py defines every bit, DESIGN.md section 4h explains the constants.
+ * Per channel, with t the index of a sample in the stream since the last reset or poisoned call:
+ *   quantise   q = rint(clamp(x * 2^qshift, +-32767)), round to nearest even, int32 (the bounds are integers, so
+ *              this is clamp(rint(..)) too, and a product that overflows is clamped). (120 + 19712) * 32767 <
+ *              2^31: every prefix sum over a call's samples and the carried ones fits int32, and so does
+ *              every accumulator below (78 * 32767 * 64 < 2^31).
+ *   correlator c(t) = sum q[t .. t+S-1] - sum q[t+S .. t+B-1]
+ *   acquire    every t < acquire_bits * B adds |c(t)| to E[t mod B] (once sample t + B - 1 is in); after the
+ *              last of them the first maximum of E is the phase, the first bit starts at
+ *              t = acquire_bits * B + phase, the previous raw bit is 0. No bits while acquiring.
+ *   track      the bit at t is decided in the call in which sample t + B arrives: raw = c(t) > 0,
+ *              bit = raw ^ previous raw, t += B. |c(t-1)|, |c(t)|, |c(t+1)| and |c(t-S)| go to the sums
+ *              early, on, late and half. After SDR_RDS_TRACK_T bits: level = on; on and half are added to the
+ *              half check's sums; then, the first that holds:
+ *                it is the (half_bits / T)-th round since the half check last ran and its half sum > its on
+ *                  sum:                        t += S, half_moves + 1
+ *                early > on and early >= late: t -= 1, moves + 1
+ *                late > on:                    t += 1, moves + 1
+ *              and the sums start again (the half check's only after its half_bits).
+ *              c(t-S) is the half-bit correlator c(t'+S) of the bit before (t' = t - B): that one ends S - 1
+ *              samples after its own bit is decided, so it is taken one bit late, when its samples are in.
+ *   state      the last SDR_RDS_TRACK_CARRY quantised samples (>= B + S + 1, what the oldest undecided bit's
+ *              correlators reach back to), the B accumulators, the sums. No block-sized buffer.
+ * A call: n = 0 is legal and changes nothing (nbits = 0). A non-finite sample anywhere in the channel's n
+ * gives nbits = SDR_NBITS_POISONED, uses none of the call's samples, and puts the channel back to acquiring
+ * with an empty stream (resets + 1; the counters stay). Bits are at least B - 1 samples apart, so n <=
+ * SDR_RDS_TRACK_MAX_N keeps nbits <= SDR_MAX_BITS; a larger n is refused. The result does not depend on how
+ * a channel's stream is cut into calls.
+ * SDR_E_INVALID, nothing enqueued: NULL handles or pointers, nch < 1, a mode sdr_rds_mode_ok refuses,
+ * options out of range, n < 0 or > SDR_RDS_TRACK_MAX_N, clean_stride < n, bits_stride < SDR_MAX_BITS. */
+#define SDR_RDS_TRACK_T 16        /* bits per early/late decision */
+#define SDR_RDS_TRACK_CARRY 120   /* quantised samples kept between calls */
+#define SDR_RDS_TRACK_MAX_N 19712 /* (SDR_MAX_BITS - 1) * (B - 1) + B - 1 */
+typedef struct sdr_rds_track_stats {   /* 32 bytes */
+    uint32_t locked;              /* 1: tracking, 0: acquiring */
+    uint32_t phase;               /* the next bit's start mod B (0 while acquiring) */
+    uint32_t bits;                /* bits emitted since the last reset */
+    uint32_t moves, half_moves;   /* +-1 sample steps, S sample steps */
+    uint32_t resets;              /* poisoned calls */
+    uint32_t level;               /* the last round's on-time sum: T bits of |c(t)| */
+    uint32_t acquired;            /* acquisitions completed */
+} sdr_rds_track_stats;
+typedef struct sdr_rds_track_opts {
+    int qshift;                   /* 0..15 */
+    int acquire_bits;             /* 1..64 */
+    int half_bits;                /* a multiple of SDR_RDS_TRACK_T in T..64 */
+} sdr_rds_track_opts;
+void sdr_rds_track_opts_default(sdr_rds_track_opts *o);   /* 10, 32, 64 */
+typedef struct sdr_rds_track sdr_rds_track;
+int sdr_rds_track_create(sdr_rds_track **out, int device, int nch, int mode, const sdr_rds_track_opts *opts);
+int sdr_rds_track_destroy(sdr_rds_track *t);
+int sdr_rds_track_reset(sdr_rds_track *t, void *stream);
+/* one kernel (one wave per channel) on `stream`, ordered behind the producer of clean_dev by the caller */
+int sdr_rds_track_bits(sdr_rds_track *t, const float *clean_dev, size_t clean_stride, int n, int32_t *nbits_dev,
+                       uint8_t *bits_dev, size_t bits_stride, void *stream);
+/* host [nch]; synchronises `stream` */
+int sdr_rds_track_stats_read(sdr_rds_track *t, sdr_rds_track_stats *host_stats, void *stream);
+
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */

@@ -13,7 +13,16 @@
  *                   a trailing "*"
  *   PREFIX.radio    at the end, every channel's sdr_rds_station_format report, each line behind
  *                   "ch <c>: ": PI, PTY (the RBDS names), TP/TA/MS, PS, RT, CT, AF, the groups by type,
- *                   blocks good/corrected/bad and BLER, slips, syncs acquired/lost. */
+ *                   blocks good/corrected/bad and BLER, slips, syncs acquired/lost.
+ *
+ * The bit clock (sdr_multi_run_rds_clock, the CLI's --rds-clock ref|track): with SDR_MULTI_RDS_CLOCK_REF the
+ * decoder reads the bits of sdr_rds_bits, as above. With SDR_MULTI_RDS_CLOCK_TRACK the RDS thread also runs
+ * the RDS symbol tracker (include/sdr_amd.h, sdr_rds_track_*) behind the block's RRC on its post stream, on the
+ * context's rds_clean row, and sdr_rds_groups reads the tracker's bits: PREFIX.groups and PREFIX.radio are made
+ * from them, and PREFIX.radio gains, behind every channel's report, the line
+ *   ch <c>: clock: locked <0|1> phase <p> bits <n> moves <m> half_moves <h> resets <r> level <l>
+ * of its sdr_rds_track_stats. PREFIX.rds, the PCM, the captures and every other file are byte for byte those
+ * of a run with the reference clock. */
 #ifndef SDR_MULTI_RDS_H
 #define SDR_MULTI_RDS_H
 
@@ -36,6 +45,17 @@ typedef struct sdr_multi_rds {
 int sdr_multi_run_rds(const sdr_multi_opts *opts, const sdr_multi_wide *wide, const sdr_multi_tuning *tune,
                       const sdr_meter_opts *mo, const sdr_audio_opts *ao, int blend, const sdr_multi_rds *rds,
                       sdr_multi_stats *stats);
+
+#define SDR_MULTI_RDS_CLOCK_REF 0     /* the bits of sdr_rds_bits: the reference's per-block clock recovery */
+#define SDR_MULTI_RDS_CLOCK_TRACK 1   /* the bits of sdr_rds_track_bits */
+
+/* sdr_multi_run_rds with a choice of bit clock; rds_clock = SDR_MULTI_RDS_CLOCK_REF is that call. track: the
+ * tracker's options, NULL for sdr_rds_track_opts_default's; only read with SDR_MULTI_RDS_CLOCK_TRACK.
+ * SDR_E_INVALID, before anything starts, also for an rds_clock that is neither, for the tracker without the
+ * decoder (rds == NULL), and for tracker options out of range. */
+int sdr_multi_run_rds_clock(const sdr_multi_opts *opts, const sdr_multi_wide *wide, const sdr_multi_tuning *tune,
+                            const sdr_meter_opts *mo, const sdr_audio_opts *ao, int blend, const sdr_multi_rds *rds,
+                            int rds_clock, const sdr_rds_track_opts *track, sdr_multi_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -118,7 +118,18 @@ class RdsStationC(C.Structure):
                [(n, C.c_uint32) for n in ("good", "corrected", "bad", "slips", "acquired", "lost")]
 
 
+class RdsTrackStats(C.Structure):
+    """sdr_rds_track_stats: one channel's bit clock, 32 bytes."""
+    _fields_ = [(n, C.c_uint32) for n in ("locked", "phase", "bits", "moves", "half_moves", "resets", "level", "acquired")]
+
+
+class RdsTrackOpts(C.Structure):
+    """sdr_rds_track_opts: the quantisation shift, the bits of acquisition and of the half-bit check."""
+    _fields_ = [("qshift", C.c_int), ("acquire_bits", C.c_int), ("half_bits", C.c_int)]
+
+
 RDS_MAX_GROUPS = 4
+RDS_TRACK_T, RDS_TRACK_CARRY, RDS_TRACK_MAX_N = 16, 120, 19712
 RDS_GROUP_CPRIME = 0x1
 METER_ROW_AUDIO, METER_ROW_RDS = 0x1, 0x2                                   # MeterRow.flags
 METER_STEREO, METER_RDS, METER_OFFTUNE, METER_DEAD_AIR = 0x1, 0x2, 0x4, 0x8   # MeterState.flags
@@ -236,6 +247,12 @@ def lib() -> C.CDLL:
         "sdr_rds_groups_read": ([vp, vp, vp, vp], i32),
         "sdr_rds_groups_copy": ([vp, vp, vp, vp], i32),
         "sdr_rds_stats_read": ([vp, vp, vp], i32),
+        "sdr_rds_track_opts_default": ([C.POINTER(RdsTrackOpts)], None),
+        "sdr_rds_track_create": ([C.POINTER(vp), i32, i32, i32, C.POINTER(RdsTrackOpts)], i32),
+        "sdr_rds_track_destroy": ([vp], i32),
+        "sdr_rds_track_reset": ([vp, vp], i32),
+        "sdr_rds_track_bits": ([vp, vp, sz, i32, vp, vp, sz, vp], i32),
+        "sdr_rds_track_stats_read": ([vp, vp, vp], i32),
         "sdr_rds_station_init": ([C.POINTER(RdsStationC)], None),
         "sdr_rds_station_update": ([C.POINTER(RdsStationC), C.POINTER(RdsGroup)], None),
         "sdr_rds_station_stats": ([C.POINTER(RdsStationC), C.POINTER(RdsStats)], None),
@@ -811,6 +828,86 @@ class RdsDecoder:
         import numpy as np
         out = np.zeros(self.nch, rds_stats_dtype())
         check(lib().sdr_rds_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_rds_stats_read")
+        return out
+
+
+def rds_track_stats_dtype():
+    """numpy dtype of sdr_rds_track_stats (32 bytes)."""
+    import numpy as np
+    return np.dtype(RdsTrackStats)
+
+
+def rds_track_opts(**opts) -> RdsTrackOpts:
+    """The tracker's defaults (sdr_rds_track_opts_default) with the given fields replaced."""
+    o = RdsTrackOpts()
+    lib().sdr_rds_track_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(RdsTrackOpts._fields_):
+            raise SdrError(f"rds_track_opts: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+class RdsTracker:
+    """The RDS symbol tracker of `nch` channels (sdr_rds_track_*): a bit clock carried from call to call and a
+    biphase correlator over the whole bit, on the GPU. Per block feed(clean) or feed_pipeline(pipe) after the
+    pipeline's rds(); the bits land in .nbits and .bits, in the layout RdsDecoder.feed takes. Mode 0 only.
+    Its own handle; the state stays on the device."""
+
+    def __init__(self, nch: int, device: int = 0, mode: int = 0, **opts):
+        import torch
+        h = C.c_void_p()
+        o = rds_track_opts(**opts)
+        check(lib().sdr_rds_track_create(C.byref(h), device, nch, mode, C.byref(o)), "sdr_rds_track_create")
+        self._h = h
+        self.nch, self.device = nch, device
+        dev = torch.device("cuda", device)
+        self.nbits = torch.zeros(nch, dtype=torch.int32, device=dev)
+        self.bits = torch.zeros(nch, SDR_MAX_BITS, dtype=torch.uint8, device=dev)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sdr_rds_track_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().sdr_rds_track_reset(self._h, _stream(stream)), "sdr_rds_track_reset")
+
+    def feed(self, clean, n: int | None = None, stream=None, nbits=None, bits=None):
+        """One call: clean is a float32 [nch][>= n] device tensor of rds_clean rows (n: its row length by
+        default); returns (nbits, bits), the tracker's own tensors unless others are given."""
+        import torch
+        if clean.dtype != torch.float32 or clean.dim() != 2 or clean.shape[0] != self.nch:
+            raise ValueError(f"clean must be a float32 [{self.nch}][n] tensor")
+        n = int(clean.shape[1]) if n is None else int(n)
+        if n > clean.shape[1]:
+            raise ValueError(f"n {n} > the row length {clean.shape[1]}")
+        nbits = self.nbits if nbits is None else nbits
+        bits = self.bits if bits is None else bits
+        if nbits.dtype != torch.int32 or tuple(nbits.shape) != (self.nch,) or not nbits.is_contiguous():
+            raise ValueError(f"nbits must be a contiguous int32 [{self.nch}] tensor")
+        if bits.dtype != torch.uint8 or bits.dim() != 2 or bits.shape[0] != self.nch or bits.shape[1] < SDR_MAX_BITS:
+            raise ValueError(f"bits must be a uint8 [{self.nch}][>= {SDR_MAX_BITS}] tensor")
+        check(lib().sdr_rds_track_bits(self._h, _ptr(clean), _row_stride(clean), n, _ptr(nbits), _ptr(bits), _row_stride(bits),
+                                       _stream(stream)), "sdr_rds_track_bits")
+        return nbits, bits
+
+    def feed_pipeline(self, pipe: "Pipeline", clean, stream=None):
+        """The rds_clean rows the pipeline's rds() of the current block returned (same stream)."""
+        return self.feed(clean, pipe.info.n_rds, stream)
+
+    def stats(self, stream=None):
+        """numpy structured array [nch] of rds_track_stats_dtype(); synchronises the stream."""
+        import numpy as np
+        out = np.zeros(self.nch, rds_track_stats_dtype())
+        check(lib().sdr_rds_track_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)),
+              "sdr_rds_track_stats_read")
         return out
 
 

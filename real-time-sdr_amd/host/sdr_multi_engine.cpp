@@ -27,6 +27,9 @@
 // device rows those bits are in; the block's group records are copied out with the bits, the frame layer
 // appends them to PREFIX.groups and feeds one sdr_rds_station per channel, and PREFIX.radio is written at
 // the end from the stations and the decoder's counters.
+// On the tracker's clock (sdr_multi_run_rds_clock) sdr_rds_track_bits runs on the same stream behind the
+// block's RRC, on the context's rds_clean row, and sdr_rds_groups reads its bits instead; sdr_rds_bits, its
+// copies and the reference frame layer run as before, so PREFIX.rds and the captures do not change.
 // Streams (the four-queue budget of DESIGN.md 5): the producer's front end and both consumers' pre
 // parts share one stream (s_fe), both consumers' post parts another (s_post), and each consumer's
 // PLL has its own CU-masked stream -- with a known block count ONE persistent launch per consumer
@@ -98,6 +101,8 @@ struct RunSpec {
     bool blend = false;                       //   its blend targets follow the meter's rows
     const sdr_multi_wide* wide = nullptr;     // wide captures (sdr_multi_run_wide)
     const sdr_multi_rds* rds = nullptr;       // the RDS group decoder (sdr_multi_run_rds)
+    int rds_clock = SDR_MULTI_RDS_CLOCK_REF;  //   whose bits it reads (sdr_multi_run_rds_clock)
+    const sdr_rds_track_opts* track = nullptr;   // the tracker's options, with SDR_MULTI_RDS_CLOCK_TRACK
 };
 
 // Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused.
@@ -113,6 +118,13 @@ bool validate(const RunSpec& r) {
     if (const sdr_multi_rds* d = r.rds)   // what sdr_rds_dec_create would refuse, and a mode without an RDS bit clock
         if (d->max_burst < 0 || d->max_burst > 5 || d->loss_blocks < 1 || d->loss_blocks > 64 || !sdr_rds_mode_ok(o->mode))
             return false;
+    if (r.rds_clock != SDR_MULTI_RDS_CLOCK_REF) {   // the tracker feeds the decoder only; what sdr_rds_track_create would refuse
+        const sdr_rds_track_opts* t = r.track;
+        if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds || !t) return false;
+        if (t->qshift < 0 || t->qshift > 15 || t->acquire_bits < 1 || t->acquire_bits > 64 || t->half_bits < SDR_RDS_TRACK_T ||
+            t->half_bits > 64 || t->half_bits % SDR_RDS_TRACK_T)
+            return false;
+    }
     if (const sdr_multi_tuning* t = r.tune) {   // the tuning's bounds (sdr_tuner_set's)
         int N = 0;
         if (sdr_tuner_table(o->mode, nullptr, 0, &N) != SDR_OK) return false;
@@ -398,7 +410,11 @@ struct RdsRes {
     sdr_rds_dec* dec = nullptr;
     Pinned<sdr_rds_group> h_groups[NH];
     Pinned<int32_t> h_ngroups[NH];
-    RdsRes(const sdr_multi_opts& o, const sdr_multi_rds* rds, bool cache) {
+    // ... on the tracker's clock (sdr_multi_run_rds_clock): the tracker and the bits it writes for the decoder
+    sdr_rds_track* trk = nullptr;
+    DevBuf<int32_t> d_tnbits;
+    DevBuf<uint8_t> d_tbits;
+    RdsRes(const sdr_multi_opts& o, const sdr_multi_rds* rds, const sdr_rds_track_opts* track, bool cache) {
         const int nch = o.nch;
         pre.make();
         pll.make();
@@ -416,8 +432,13 @@ struct RdsRes {
             h_groups[h].take((size_t)nch * SDR_RDS_MAX_GROUPS * sizeof(sdr_rds_group), cache);
             h_ngroups[h].take(nch * sizeof(int32_t), cache);
         }
+        if (!track) return;
+        check_sdr(sdr_rds_track_create(&trk, o.device, nch, o.mode, track), "sdr_rds_track_create");
+        d_tnbits.get((size_t)nch);
+        d_tbits.get((size_t)nch * SDR_MAX_BITS);
     }
     ~RdsRes() {
+        if (trk) (void)sdr_rds_track_destroy(trk);
         if (dec) (void)sdr_rds_dec_destroy(dec);
     }
 };
@@ -899,8 +920,18 @@ void rds_thread(Shared* sh) {
         check_sdr(sdr_rds_bits(ctx, nullptr, nullptr, nullptr, 0, r.d_nbits.p, r.d_bits.p, SDR_MAX_BITS, s), "sdr_rds_bits");
         check_hip(hipMemcpyAsync(r.h_nbits[k], r.d_nbits.p, o.nch * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
         check_hip(hipMemcpyAsync(r.h_bits[k], r.d_bits.p, (size_t)o.nch * SDR_MAX_BITS, hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+        if (r.trk) {   // the block's rds_clean row, behind its RRC on this stream, into bits of the same layout
+            const float* clean = nullptr;
+            size_t clean_stride = 0;
+            int n_rds = 0;
+            check_sdr(sdr_ctx_buffer(ctx, "rds_clean", &clean, &clean_stride, &n_rds), "sdr_ctx_buffer");
+            check_sdr(sdr_rds_track_bits(r.trk, clean, clean_stride, n_rds, r.d_tnbits.p, r.d_tbits.p, SDR_MAX_BITS, s),
+                      "sdr_rds_track_bits");
+        }
         if (r.dec) {   // on the bits where they are; the last block's stream follows the others' (consumer_pll)
-            check_sdr(sdr_rds_groups(r.dec, r.d_nbits.p, r.d_bits.p, SDR_MAX_BITS, s), "sdr_rds_groups");
+            const int32_t* nbits = r.trk ? r.d_tnbits.p : r.d_nbits.p;
+            const uint8_t* bits = r.trk ? r.d_tbits.p : r.d_bits.p;
+            check_sdr(sdr_rds_groups(r.dec, nbits, bits, SDR_MAX_BITS, s), "sdr_rds_groups");
             check_sdr(sdr_rds_groups_copy(r.dec, r.h_groups[k], r.h_ngroups[k], s), "sdr_rds_groups_copy");
         }
         check_hip(hipEventRecord(r.out_ready[k], s), "hipEventRecord");
@@ -959,6 +990,8 @@ void rds_thread(Shared* sh) {
     if (r.dec) {   // PREFIX.radio: what every station said, and how well it was received
         std::vector<sdr_rds_stats> stats((size_t)o.nch);
         check_sdr(sdr_rds_stats_read(r.dec, stats.data(), sh->s_post_c[1]), "sdr_rds_stats_read");
+        std::vector<sdr_rds_track_stats> clock(r.trk ? (size_t)o.nch : 0);
+        if (r.trk) check_sdr(sdr_rds_track_stats_read(r.trk, clock.data(), sh->s_post_c[1]), "sdr_rds_track_stats_read");
         File radio;
         radio.open(std::string(o.out_prefix) + ".radio", "w");
         std::vector<char> buf(4096);
@@ -967,6 +1000,10 @@ void rds_thread(Shared* sh) {
             sdr_rds_station_format(&stations[(size_t)c], buf.data(), buf.size());
             std::istringstream lines(buf.data());
             for (std::string line; std::getline(lines, line);) std::fprintf(radio, "ch %d: %s\n", c, line.c_str());
+            if (!r.trk) continue;
+            const sdr_rds_track_stats& k = clock[(size_t)c];
+            std::fprintf(radio, "ch %d: clock: locked %u phase %u bits %u moves %u half_moves %u resets %u level %u\n", c, k.locked,
+                         k.phase, k.bits, k.moves, k.half_moves, k.resets, k.level);
         }
     }
     File f;
@@ -1057,7 +1094,7 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     mark("streams");
     const size_t lr_bytes = 2 * (size_t)sh.info.n_audio * o.nch * sizeof(int16_t);
     sh.ar.emplace(lr_bytes, sw.pin_cache);
-    sh.rr.emplace(o, spec.rds, sw.pin_cache);
+    sh.rr.emplace(o, spec.rds, spec.rds_clock == SDR_MULTI_RDS_CLOCK_TRACK ? spec.track : nullptr, sw.pin_cache);
     if (spec.meter) sh.meter.emplace(o, *spec.meter, sw.pin_cache);
     if (spec.audio) sh.fin.emplace(o, *spec.audio, spec.blend, lr_bytes, sw.pin_cache);
     mark("consumer buffers");
@@ -1158,4 +1195,14 @@ extern "C" int sdr_multi_run_rds(const sdr_multi_opts* opts, const sdr_multi_wid
     if (!rds) return sdr_multi_run_wide(opts, wide, tune, mo, ao, blend, stats);
     if (wide && !tune) return SDR_E_INVALID;
     return multi_run({opts, tune, mo, ao, blend != 0, wide, rds}, stats);
+}
+
+extern "C" int sdr_multi_run_rds_clock(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
+                                       const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, const sdr_multi_rds* rds,
+                                       int rds_clock, const sdr_rds_track_opts* track, sdr_multi_stats* stats) {
+    if (rds_clock == SDR_MULTI_RDS_CLOCK_REF) return sdr_multi_run_rds(opts, wide, tune, mo, ao, blend, rds, stats);
+    if (!rds || (wide && !tune)) return SDR_E_INVALID;
+    sdr_rds_track_opts defaults;
+    sdr_rds_track_opts_default(&defaults);
+    return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, rds_clock, track ? track : &defaults}, stats);
 }
