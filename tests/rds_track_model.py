@@ -203,3 +203,69 @@ def noise_rows(seed: int, n: int, amp_q: int = 300, sigma_q: int = 200) -> tuple
     bits = rs.integers(0, 2, nb)
     x = chips(bits, float(amp_q))[:n] + rs.integers(-sigma_q, sigma_q + 1, n).astype(np.float32)
     return (x / np.float32(1 << QSHIFT)).astype(np.float32), [int(b) for b in bits]
+
+
+def for_qshift(x, qshift: int) -> np.ndarray:
+    """x, made for QSHIFT, scaled by the power of two that gives the same x * 2^qshift (exact in f32 for the
+    samples of noise_rows and wrong_half; off_grid takes qshift itself, its +-3e38 would overflow here)."""
+    return (np.asarray(x, np.float32) * np.float32(2.0 ** (QSHIFT - qshift))).astype(np.float32)
+
+
+OFF_GRID_SPECIALS = (3e38, -3e38, 1e-40, -0.0, 32.0, 31.9985)   # 32.0 and 31.9985 are in units of 2^(QSHIFT - qshift)
+
+
+def off_grid(seed: int, n: int, qshift: int = QSHIFT, amp_q: int = 300, sigma_q: int = 200, gain: float = 1.0,
+             quiet_tail: int = 0) -> np.ndarray:
+    """n samples that the quantisation has to round: noise_rows times f32 factors drawn from [0.9, 1.1] (and
+    `gain`), then, everywhere but in the last quiet_tail samples, a sprinkling of exact ties (k + 0.5) * 2^-qshift
+    of both signs, and OFF_GRID_SPECIALS four times each: products that overflow before the clamp, a subnormal,
+    -0.0, the clamp's bound and the last value below it. For another qshift the same quantised stream."""
+    rs = np.random.Generator(np.random.PCG64(seed))
+    x = noise_rows(seed, n, amp_q, sigma_q)[0] * rs.uniform(0.9, 1.1, n).astype(np.float32) * np.float32(gain)
+    x = for_qshift(x, qshift)
+    nties = max(64, n // 40)
+    at = rs.permutation(n - quiet_tail)[:nties + 4 * len(OFF_GRID_SPECIALS)]
+    assert len(at) == nties + 4 * len(OFF_GRID_SPECIALS), "off_grid: n is too small for its sprinkling"
+    k = rs.integers(-400, 400, nties).astype(np.float32)                     # k + 0.5: -399.5 .. 399.5
+    x[at[:nties]] = (k + np.float32(0.5)) / np.float32(1 << qshift)
+    special = np.array(OFF_GRID_SPECIALS, np.float32)
+    special[4:] = for_qshift(special[4:], qshift)
+    x[at[nties:]] = np.tile(special, 4)
+    return x
+
+
+def walking(seed: int, n: int, every: int, doubled: bool, amp_q: int = 300, sigma_q: int = 200) -> np.ndarray:
+    """n samples of noise_rows with one sample in every `every` deleted (or doubled): at every = 16 B - 1
+    deleted the clock steps early each round of T bits, at 16 B + 1 doubled it steps late each round."""
+    steps = n // every
+    x = noise_rows(seed, n + steps, amp_q, sigma_q)[0]
+    at = np.arange(1, steps + 1) * every - 1
+    return (np.insert(x, at, x[at]) if doubled else np.delete(x, at))[:n]
+
+
+CHUNK = 3072                                   # k_rds_track stages a call in chunks of this many samples (TRK_CHUNK)
+BOUNDARY_SIZES = (0, 1, 2, 3, 4, 5, CARRY - 1, CARRY, CARRY + 1, CHUNK - 1, CHUNK, CHUNK + 1, CHUNK + 3, 2 * CHUNK,
+                  2 * CHUNK + 1, MAX_N - 1, MAX_N)
+
+
+def boundary_plan(seed: int, ncalls: int = 40) -> list:
+    """Call lengths at the kernel's edges: every one of BOUNDARY_SIZES once and further ones of at most two
+    chunks and a sample, in a seeded order."""
+    rs = np.random.Generator(np.random.PCG64(seed))
+    small = [n for n in BOUNDARY_SIZES if n <= 2 * CHUNK + 1]
+    plan = list(BOUNDARY_SIZES) + [int(v) for v in rs.choice(small, ncalls - len(BOUNDARY_SIZES))]
+    plan = [plan[i] for i in rs.permutation(len(plan))]
+    assert set(plan) == set(BOUNDARY_SIZES) and len(plan) == ncalls
+    return plan
+
+
+def wrong_half(seed: int, n: int, acquire_bits: int = A, amp_q: int = 300, sigma_q: int = 150) -> np.ndarray:
+    """n samples whose acquisition takes the wrong half: acquire_bits + 4 zero bits without noise (the two
+    alignments are then equal and the first maximum is the smaller residue), then noisy data; the right phase
+    is 50, acquisition takes 50 - S = 11."""
+    rs = np.random.Generator(np.random.PCG64(seed))
+    bits = [0] * (acquire_bits + 4) + [int(v) for v in rs.integers(0, 2, n // B + 3)]
+    x = chips(bits, float(amp_q))[(-50) % B:][:n]
+    quiet = (acquire_bits + 3) * B
+    x[quiet:] += rs.integers(-sigma_q, sigma_q + 1, max(n - quiet, 0)).astype(np.float32)
+    return (x / np.float32(1 << QSHIFT)).astype(np.float32)

@@ -85,8 +85,8 @@ def test_wrong_half_is_left():
 
 
 # ---------------------------------------------------------------- call-cut invariance
-def _feed(x, sizes):
-    ch, out, at, ncalls = tm.Channel(), [], 0, 0
+def _feed(x, sizes, **opts):
+    ch, out, at, ncalls = tm.Channel(**opts), [], 0, 0
     for n in sizes:
         n = min(n, len(x) - at)
         nb, bits = ch.call(x[at:at + n])
@@ -113,6 +113,76 @@ def test_call_cut_invariance():
         got, st = _feed(x, sizes)
         assert got == want, name
         assert st == state, name
+
+
+OPTION_SETS = (dict(acquire_bits=1), dict(acquire_bits=64), dict(half_bits=16), dict(half_bits=32), dict(qshift=0),
+               dict(qshift=15))
+
+
+@pytest.mark.parametrize("opts", OPTION_SETS, ids=lambda o: ",".join(f"{k}={v}" for k, v in o.items()))
+def test_call_cut_invariance_under_options(opts):
+    """Every option away from its default, on a stream that has to be rounded and whose clock steps: the cut
+    into calls changes neither the bits nor the state, at the lengths around the kernel's chunk and carry too."""
+    n = sum(tm.BOUNDARY_SIZES)
+    q = opts.get("qshift", tm.QSHIFT)
+    x = np.delete(tm.off_grid(7, n + 2, qshift=q), [3 * ROW + 500, 6 * ROW + 7])
+    assert np.array_equal(tm.quantise(x, q), np.delete(tm.quantise(tm.off_grid(7, n + 2)), [3 * ROW + 500, 6 * ROW + 7]))
+    want, state = _feed(x, [ROW] * (n // ROW + 1), **opts)
+    st = dict(zip(tm.STATS, state[-len(tm.STATS):]))
+    assert len(want) > 700 and st["locked"] == 1 and st["moves"] >= 1, st
+    plans = {"uneven": [1, 77, 2836, 0, 78, 1000, 79, 4097, 3071, 3073] * 5, "boundaries": tm.boundary_plan(8, 17)}
+    assert sum(plans["uneven"]) >= n and sum(plans["boundaries"]) == n
+    for name, sizes in plans.items():
+        got, st = _feed(x, sizes, **opts)
+        assert got == want, name
+        assert st == state, name
+
+
+def test_a_shorter_half_check_leaves_the_wrong_half_earlier():
+    left = {}
+    for hb in (16, 64):
+        ch, x = tm.Channel(half_bits=hb), tm.wrong_half(3, 12 * ROW)
+        for k in range(0, len(x), B):
+            ch.call(x[k:k + B])
+            if ch.half_moves and hb not in left:
+                left[hb] = k
+        st = ch.stats()
+        assert st["locked"] == 1 and st["half_moves"] == 1 and st["phase"] == 50 and st["acquired"] == 1, (hb, st)
+    assert left[16] < left[64], left
+
+
+@pytest.mark.parametrize("value", [0.0, 0.25, -0.0])
+@pytest.mark.parametrize("acquire_bits", [1, 32, 64])
+def test_silence_locks_at_phase_zero_and_gives_zero_bits(value, acquire_bits):
+    """Every E is equal, so the first maximum is residue 0; every correlator is 0, so nothing moves."""
+    ch = tm.Channel(acquire_bits=acquire_bits)
+    need = (acquire_bits + 1) * B - 1                              # the last acquisition position's last sample
+    x = np.full(need + 5 * ROW, value, np.float32)
+    assert ch.call(x[:need - 1]) == (0, []) and not ch.locked
+    assert ch.call(x[need - 1:need]) == (0, []) and ch.locked and ch.t == acquire_bits * B
+    out = []
+    for r in _rows(x[need:]):
+        out += ch.call(r)[1]
+    assert len(out) == (len(x) - 1) // B - acquire_bits and not any(out)
+    assert ch.stats() == dict(locked=1, phase=0, bits=len(out), moves=0, half_moves=0, resets=0, level=0, acquired=1)
+
+
+def test_the_stream_builders_are_what_they_say():
+    k = np.float32(1 << tm.QSHIFT)
+    x = tm.off_grid(9, 20000)
+    y = x.astype(np.float64) * float(k)
+    assert np.mean(y != np.rint(y)) >= 0.9
+    assert np.sum(np.abs(y - np.floor(y) - 0.5) == 0) >= 50 and np.isfinite(x).all()
+    for v in tm.OFF_GRID_SPECIALS:
+        assert np.sum(x.view(np.uint32) == np.float32(v).view(np.uint32)) >= 4, v
+    for qs in (0, 15):
+        assert np.array_equal(tm.quantise(tm.off_grid(9, 20000, qshift=qs), qs), tm.quantise(x))
+    base = tm.noise_rows(21, 4003)[0]                              # three steps in 4000 samples
+    d, i = tm.walking(21, 4000, 1247, False), tm.walking(21, 4000, 1249, True)
+    assert np.array_equal(d[:1246], base[:1246]) and np.array_equal(d[1246:2492], base[1247:2493])
+    assert np.array_equal(i[:1249], base[:1249]) and i[1249] == base[1248] and np.array_equal(i[1250:2498], base[1249:2497])
+    plan = tm.boundary_plan(1)
+    assert len(plan) == 40 and set(plan) == set(tm.BOUNDARY_SIZES)
 
 
 # ---------------------------------------------------------------- poison and reset
