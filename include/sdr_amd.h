@@ -625,6 +625,55 @@ int sdr_rds_track_bits(sdr_rds_track *t, const float *clean_dev, size_t clean_st
 /* host [nch]; synchronises `stream` */
 int sdr_rds_track_stats_read(sdr_rds_track *t, sdr_rds_track_stats *host_stats, void *stream);
 
+/* ---- RDS soft decisions (no reference counterpart; callers detect them by symbol): the tracker's per-bit
+ * reliabilities and a Chase step of the group decoder over the least reliable raw decisions of a failing
+ * block. Additive: every call above keeps its results. All integer; tests/rds_soft_model.py defines every
+ * bit, DESIGN.md section 4i explains the rules.
+ * Tracker: sdr_rds_track_bits_soft is sdr_rds_track_bits (the same state, clock, nbits, bits and stats) that
+ *   also writes soft [nch][soft_stride] u16: soft[k] = |c(t)| >> 6 of raw decision k, the one whose XOR with
+ *   raw k-1 is bit k (78 * 32767 >> 6 = 39934: no clamp). A poisoned call writes no soft values.
+ * Decoder: a handle of sdr_rds_dec_create_soft takes sdr_rds_groups_soft, a handle of sdr_rds_dec_create
+ *   sdr_rds_groups, and each refuses the other call. soft_bits = L in 0..6; L = 0 decodes like
+ *   sdr_rds_groups bit for bit. The handle keeps the soft values of the last 32 bits a channel consumed. At a
+ *   judgement at bit i, between steps 3 and 4 of the list above, on the nominal word only:
+ *     candidates  the 27 raw decisions i-27 .. i-1 stand behind diff bits i-26 .. i-1; the L of them with the
+ *                 smallest (soft, position), older first on ties
+ *     patterns    m = 1 .. 2^L - 1 flips the candidates whose bit is set in m (bit j: the j-th candidate in
+ *                 that order); a flipped raw r toggles diff bits r and r+1, clipped to the window, so the two
+ *                 edge raws toggle one bit each; e(m) is the XOR, never 0
+ *     weight      w(m) = the sum of the flipped candidates' soft (< 2^19)
+ *     acceptance  of all m whose nominal ^ e(m) matches an offset of block expect (C before C'), the smallest
+ *                 (w, m) wins
+ *     effect      as step 4: the word is placed, its bit goes into ok and corrected, corrected + 1, bad_run
+ *                 stays, next at i + 26; its bit also goes into the group's flags at SDR_RDS_GROUP_SOFT_SHIFT;
+ *                 soft_blocks + 1, soft_flips + popcount(m). No m matches: steps 4 and 5 as above.
+ *   A call consumes nbits soft values with its bits; -1 and invalid nbits consume nothing; SDR_NBITS_POISONED
+ *   as above. No judgement's window reaches across a reset, a loss of sync or a poisoned call: sync is
+ *   dropped and the pending hit cleared there, and the first window after an acquisition at bit i is i .. i+26.
+ *   The result does not depend on how a channel's stream is cut into calls.
+ * SDR_E_INVALID, nothing enqueued: as for the calls above, and NULL soft_dev, soft_stride < SDR_MAX_BITS,
+ * soft_bits outside 0..6, the wrong kind of handle. */
+#define SDR_RDS_GROUP_SOFT_SHIFT 4   /* sdr_rds_group.flags bit 4 + b: block b was placed by the soft step */
+#define SDR_RDS_SOFT_HISTORY 32      /* soft values kept per channel between calls (>= 28) */
+typedef struct sdr_rds_soft_opts {
+    int max_burst, loss_blocks;  /* as sdr_rds_opts */
+    int soft_bits;               /* 0..6 */
+} sdr_rds_soft_opts;
+void sdr_rds_soft_opts_default(sdr_rds_soft_opts *o);   /* 2, 8, 6 */
+typedef struct sdr_rds_soft_stats {   /* 16 bytes */
+    uint32_t soft_blocks;        /* blocks placed by the soft step (they count in sdr_rds_stats.corrected too) */
+    uint32_t soft_flips;         /* raw decisions flipped in them */
+    uint32_t soft_bits;          /* the handle's option */
+    uint32_t reserved;           /* 0 */
+} sdr_rds_soft_stats;
+int sdr_rds_track_bits_soft(sdr_rds_track *t, const float *clean_dev, size_t clean_stride, int n, int32_t *nbits_dev,
+                            uint8_t *bits_dev, size_t bits_stride, uint16_t *soft_dev, size_t soft_stride, void *stream);
+int sdr_rds_dec_create_soft(sdr_rds_dec **out, int device, int nch, const sdr_rds_soft_opts *opts);
+int sdr_rds_groups_soft(sdr_rds_dec *d, const int32_t *nbits_dev, const uint8_t *bits_dev, size_t bits_stride,
+                        const uint16_t *soft_dev, size_t soft_stride, void *stream);
+/* host [nch]; synchronises `stream`; a handle of sdr_rds_dec_create reads as zeros */
+int sdr_rds_soft_stats_read(sdr_rds_dec *d, sdr_rds_soft_stats *host_stats, void *stream);
+
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */

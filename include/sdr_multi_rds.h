@@ -57,6 +57,21 @@ int sdr_multi_run_rds_clock(const sdr_multi_opts *opts, const sdr_multi_wide *wi
                             const sdr_meter_opts *mo, const sdr_audio_opts *ao, int blend, const sdr_multi_rds *rds,
                             int rds_clock, const sdr_rds_track_opts *track, sdr_multi_stats *stats);
 
+/* sdr_multi_run_rds_clock with soft decisions (the CLI's --rds-soft L); soft == NULL is that call. With soft the
+ * RDS thread runs sdr_rds_track_bits_soft, which also writes every bit's reliability into one more
+ * [nch][SDR_MAX_BITS] u16 device row set of the engine's pool, and sdr_rds_groups_soft on a decoder of
+ * sdr_rds_dec_create_soft(soft): soft->max_burst and soft->loss_blocks are the decoder's, rds only says that
+ * the run decodes. In PREFIX.groups a block the soft step placed ends in "~" instead of "*", and PREFIX.radio
+ * gains, behind every channel's clock line, the line
+ *   ch <c>: soft: blocks <n> flips <f>
+ * of its sdr_rds_soft_stats. Every other file is byte for byte that of the run without soft.
+ * SDR_E_INVALID, before anything starts, also for soft without SDR_MULTI_RDS_CLOCK_TRACK or without rds, and for
+ * soft options out of range (soft_bits 0..6). */
+int sdr_multi_run_rds_soft(const sdr_multi_opts *opts, const sdr_multi_wide *wide, const sdr_multi_tuning *tune,
+                           const sdr_meter_opts *mo, const sdr_audio_opts *ao, int blend, const sdr_multi_rds *rds,
+                           int rds_clock, const sdr_rds_track_opts *track, const sdr_rds_soft_opts *soft,
+                           sdr_multi_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

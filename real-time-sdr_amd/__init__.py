@@ -128,7 +128,18 @@ class RdsTrackOpts(C.Structure):
     _fields_ = [("qshift", C.c_int), ("acquire_bits", C.c_int), ("half_bits", C.c_int)]
 
 
+class RdsSoftOpts(C.Structure):
+    """sdr_rds_soft_opts: sdr_rds_opts and the number of least reliable raw decisions the soft step may flip."""
+    _fields_ = [("max_burst", C.c_int), ("loss_blocks", C.c_int), ("soft_bits", C.c_int)]
+
+
+class RdsSoftStats(C.Structure):
+    """sdr_rds_soft_stats: one channel's soft-step counters, 16 bytes."""
+    _fields_ = [(n, C.c_uint32) for n in ("soft_blocks", "soft_flips", "soft_bits", "reserved")]
+
+
 RDS_MAX_GROUPS = 4
+RDS_GROUP_SOFT_SHIFT, RDS_SOFT_HISTORY = 4, 32
 RDS_TRACK_T, RDS_TRACK_CARRY, RDS_TRACK_MAX_N = 16, 120, 19712
 RDS_GROUP_CPRIME = 0x1
 METER_ROW_AUDIO, METER_ROW_RDS = 0x1, 0x2                                   # MeterRow.flags
@@ -247,6 +258,11 @@ def lib() -> C.CDLL:
         "sdr_rds_groups_read": ([vp, vp, vp, vp], i32),
         "sdr_rds_groups_copy": ([vp, vp, vp, vp], i32),
         "sdr_rds_stats_read": ([vp, vp, vp], i32),
+        "sdr_rds_soft_opts_default": ([C.POINTER(RdsSoftOpts)], None),
+        "sdr_rds_dec_create_soft": ([C.POINTER(vp), i32, i32, C.POINTER(RdsSoftOpts)], i32),
+        "sdr_rds_groups_soft": ([vp, vp, vp, sz, vp, sz, vp], i32),
+        "sdr_rds_soft_stats_read": ([vp, vp, vp], i32),
+        "sdr_rds_track_bits_soft": ([vp, vp, sz, i32, vp, vp, sz, vp, sz, vp], i32),
         "sdr_rds_track_opts_default": ([C.POINTER(RdsTrackOpts)], None),
         "sdr_rds_track_create": ([C.POINTER(vp), i32, i32, i32, C.POINTER(RdsTrackOpts)], i32),
         "sdr_rds_track_destroy": ([vp], i32),
@@ -773,15 +789,41 @@ def rds_opts(**opts) -> RdsOpts:
     return o
 
 
+def rds_soft_opts(**opts) -> RdsSoftOpts:
+    """The soft decoder's defaults (sdr_rds_soft_opts_default) with the given fields replaced."""
+    o = RdsSoftOpts()
+    lib().sdr_rds_soft_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(RdsSoftOpts._fields_):
+            raise SdrError(f"rds_soft_opts: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+def rds_soft_stats_dtype():
+    """numpy dtype of sdr_rds_soft_stats (16 bytes)."""
+    import numpy as np
+    return np.dtype(RdsSoftStats)
+
+
 class RdsDecoder:
     """The RDS group decoder of `nch` channels (sdr_rds_*): block sync with a flywheel, slip recovery and
     burst correction on the GPU. Per block feed(nbits, bits) or feed_pipeline(pipe) after the pipeline's
-    rds(); groups() returns that call's group records. Its own handle; the state stays on the device."""
+    rds(); groups() returns that call's group records. Its own handle; the state stays on the device.
+    soft_bits > 0 (or soft=True, for a soft handle at soft_bits 0) makes a handle of sdr_rds_dec_create_soft:
+    feed then needs the tracker's soft row, and a failing block is first searched over its soft_bits least
+    reliable raw decisions."""
 
-    def __init__(self, nch: int, device: int = 0, max_burst: int = 2, loss_blocks: int = 8):
+    def __init__(self, nch: int, device: int = 0, max_burst: int = 2, loss_blocks: int = 8, soft_bits: int = 0,
+                 soft: bool | None = None):
         h = C.c_void_p()
-        o = rds_opts(max_burst=max_burst, loss_blocks=loss_blocks)
-        check(lib().sdr_rds_dec_create(C.byref(h), device, nch, C.byref(o)), "sdr_rds_dec_create")
+        self.soft = bool(soft_bits) if soft is None else bool(soft)
+        if self.soft:
+            so = rds_soft_opts(max_burst=max_burst, loss_blocks=loss_blocks, soft_bits=soft_bits)
+            check(lib().sdr_rds_dec_create_soft(C.byref(h), device, nch, C.byref(so)), "sdr_rds_dec_create_soft")
+        else:
+            o = rds_opts(max_burst=max_burst, loss_blocks=loss_blocks)
+            check(lib().sdr_rds_dec_create(C.byref(h), device, nch, C.byref(o)), "sdr_rds_dec_create")
         self._h = h
         self.nch, self.device = nch, device
 
@@ -799,13 +841,21 @@ class RdsDecoder:
     def reset(self, stream=None):
         check(lib().sdr_rds_dec_reset(self._h, _stream(stream)), "sdr_rds_dec_reset")
 
-    def feed(self, nbits, bits, stream=None):
-        """One call: nbits int32 [nch] and bits uint8 [nch][>= SDR_MAX_BITS] device tensors."""
+    def feed(self, nbits, bits, stream=None, soft=None):
+        """One call: nbits int32 [nch] and bits uint8 [nch][>= SDR_MAX_BITS] device tensors; soft: the uint16
+        (or int16 storage) [nch][>= SDR_MAX_BITS] reliabilities of those bits, for a soft handle."""
         import torch
         if nbits.dtype != torch.int32 or tuple(nbits.shape) != (self.nch,) or not nbits.is_contiguous():
             raise ValueError(f"nbits must be a contiguous int32 [{self.nch}] tensor")
         if bits.dtype != torch.uint8 or bits.dim() != 2 or bits.shape[0] != self.nch or bits.shape[1] < SDR_MAX_BITS:
             raise ValueError(f"bits must be a uint8 [{self.nch}][>= {SDR_MAX_BITS}] tensor")
+        if soft is not None:
+            if soft.element_size() != 2 or soft.is_floating_point() or soft.dim() != 2 or soft.shape[0] != self.nch \
+                    or soft.shape[1] < SDR_MAX_BITS:
+                raise ValueError(f"soft must be a 16-bit integer [{self.nch}][>= {SDR_MAX_BITS}] tensor")
+            check(lib().sdr_rds_groups_soft(self._h, _ptr(nbits), _ptr(bits), _row_stride(bits), _ptr(soft),
+                                            _row_stride(soft), _stream(stream)), "sdr_rds_groups_soft")
+            return
         check(lib().sdr_rds_groups(self._h, _ptr(nbits), _ptr(bits), _row_stride(bits), _stream(stream)),
               "sdr_rds_groups")
 
@@ -828,6 +878,15 @@ class RdsDecoder:
         import numpy as np
         out = np.zeros(self.nch, rds_stats_dtype())
         check(lib().sdr_rds_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_rds_stats_read")
+        return out
+
+
+    def soft_stats(self, stream=None):
+        """numpy structured array [nch] of rds_soft_stats_dtype(); synchronises the stream."""
+        import numpy as np
+        out = np.zeros(self.nch, rds_soft_stats_dtype())
+        check(lib().sdr_rds_soft_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)),
+              "sdr_rds_soft_stats_read")
         return out
 
 
@@ -864,6 +923,7 @@ class RdsTracker:
         dev = torch.device("cuda", device)
         self.nbits = torch.zeros(nch, dtype=torch.int32, device=dev)
         self.bits = torch.zeros(nch, SDR_MAX_BITS, dtype=torch.uint8, device=dev)
+        self.soft = None                 # the reliabilities of .bits, allocated by the first feed(..., soft=True)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -879,9 +939,12 @@ class RdsTracker:
     def reset(self, stream=None):
         check(lib().sdr_rds_track_reset(self._h, _stream(stream)), "sdr_rds_track_reset")
 
-    def feed(self, clean, n: int | None = None, stream=None, nbits=None, bits=None):
+    def feed(self, clean, n: int | None = None, stream=None, nbits=None, bits=None, soft=None):
         """One call: clean is a float32 [nch][>= n] device tensor of rds_clean rows (n: its row length by
-        default); returns (nbits, bits), the tracker's own tensors unless others are given."""
+        default); returns (nbits, bits), the tracker's own tensors unless others are given. soft: True for
+        the tracker's own .soft (int16 storage of the u16 values, allocated on first use) or a 16-bit integer
+        [nch][>= SDR_MAX_BITS] tensor; the call then also writes every bit's reliability and returns
+        (nbits, bits, soft)."""
         import torch
         if clean.dtype != torch.float32 or clean.dim() != 2 or clean.shape[0] != self.nch:
             raise ValueError(f"clean must be a float32 [{self.nch}][n] tensor")
@@ -894,6 +957,18 @@ class RdsTracker:
             raise ValueError(f"nbits must be a contiguous int32 [{self.nch}] tensor")
         if bits.dtype != torch.uint8 or bits.dim() != 2 or bits.shape[0] != self.nch or bits.shape[1] < SDR_MAX_BITS:
             raise ValueError(f"bits must be a uint8 [{self.nch}][>= {SDR_MAX_BITS}] tensor")
+        if soft is not None and soft is not False:
+            if soft is True:
+                if self.soft is None:
+                    self.soft = torch.zeros(self.nch, SDR_MAX_BITS, dtype=torch.int16, device=bits.device)
+                soft = self.soft
+            if soft.element_size() != 2 or soft.is_floating_point() or soft.dim() != 2 or soft.shape[0] != self.nch \
+                    or soft.shape[1] < SDR_MAX_BITS:
+                raise ValueError(f"soft must be a 16-bit integer [{self.nch}][>= {SDR_MAX_BITS}] tensor")
+            check(lib().sdr_rds_track_bits_soft(self._h, _ptr(clean), _row_stride(clean), n, _ptr(nbits), _ptr(bits),
+                                                _row_stride(bits), _ptr(soft), _row_stride(soft), _stream(stream)),
+                  "sdr_rds_track_bits_soft")
+            return nbits, bits, soft
         check(lib().sdr_rds_track_bits(self._h, _ptr(clean), _row_stride(clean), n, _ptr(nbits), _ptr(bits), _row_stride(bits),
                                        _stream(stream)), "sdr_rds_track_bits")
         return nbits, bits

@@ -11,8 +11,10 @@
 //   sdr_scan.hip       band scan of the capture rows
 //   sdr_meter.hip      reception meter: per-channel readings of a block's rows
 //   sdr_split.hip      wideband splitter: a wide s8 capture into the capture rows (its own handle)
-//   sdr_rds.hip        RDS group decoder over the bits of sdr_rds_bits or the tracker (its own handle)
-//   sdr_rds_track.hip  RDS symbol tracker: rds_clean rows into bits on a continuous bit clock (its own handle)
+//   sdr_rds.hip        RDS group decoder over the bits of sdr_rds_bits or the tracker (its own handle); with the
+//                      tracker's soft values, a search over a failing block's least reliable bits (sdr_rds_*_soft)
+//   sdr_rds_track.hip  RDS symbol tracker: rds_clean rows into bits on a continuous bit clock (its own handle),
+//                      and each bit's reliability (sdr_rds_track_bits_soft)
 //
 // Layout: channel-major [nch][len]. Every f32 stream that a later FIR/resampler reads with
 // look-back is kept "extended": [2 parities][nch][HIST + len], the first HIST samples being the

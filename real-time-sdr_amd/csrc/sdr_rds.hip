@@ -26,6 +26,11 @@ struct sdr_rds_dec {
     sdr_rds_group* groups = nullptr;   // [nch][SDR_RDS_MAX_GROUPS] (device)
     int32_t* ngroups = nullptr;     // [nch] (device)
     sdr_rds_stats* stats = nullptr; // [nch] (device), gathered by k_rds_stats
+    // a handle of sdr_rds_dec_create_soft
+    bool soft = false;
+    int soft_bits = 0;
+    uint16_t* hist = nullptr;       // [nch][SDR_RDS_SOFT_HISTORY] the soft values of the last bits consumed (device)
+    sdr_rds_soft_stats* sstats = nullptr;   // [nch] (device), gathered by k_rds_soft_stats
 };
 
 namespace sdrk {
@@ -44,7 +49,8 @@ struct alignas(64) RdsState {      // 128 bytes
     uint8_t ok, corrected, flags, synced;
     int32_t expect, bad_run, pend_idx;   // pend_idx < 0: no pending hit
     uint32_t good, ncorrected, bad, slips, acquired, lost, groups;
-    uint32_t pad[11];
+    uint32_t soft_blocks, soft_flips;    // the soft step's counters (zero on a handle without it)
+    uint32_t pad[9];
 };
 static_assert(sizeof(RdsState) == 128, "RdsState is two 64-byte lines");
 
@@ -74,12 +80,62 @@ __device__ __forceinline__ int match_block(uint32_t s, int blk) {
     return s == OFFW[o] ? o : -1;
 }
 
+constexpr int SOFT_WIN = 27;       // raw decisions behind the 26 diff bits of a word
+constexpr int SOFT_HIST = SDR_RDS_SOFT_HISTORY;
+static_assert(SOFT_HIST >= SOFT_WIN + 1, "the history holds a window that ends one bit before the call's first");
+
+// the diff bits of the nominal word that flipping window raw p (0 = the oldest) toggles: r and r + 1, clipped
+__device__ __forceinline__ uint32_t soft_toggle(int p) { return ((3u << 26) >> (p + 1)) & M26; }
+
+// The soft step of a failing block (wave-parallel, every lane returns the same): sv[0 .. 26] are the window's
+// soft values, the oldest first. Lanes 0..26 rank them by counting smaller (soft, position) pairs, the L
+// lowest ranks publish their toggle mask and soft, lane m builds e(m) and w(m) and the syndrome of
+// nominal ^ e(m), and a wave minimum of w * 64 + m (< 2^25) over the matching lanes picks the winner.
+// Returns e of the winner (never 0) and its offset and m, or 0.
+__device__ __forceinline__ uint32_t soft_search(const uint16_t* sv, uint32_t* cmask, uint32_t* csoft, uint32_t nominal,
+                                                int expect, int L, const ParityRows& pr, int lane, int* o_out, int* m_out) {
+    if (lane < SOFT_WIN) {
+        const uint32_t mine = ((uint32_t)sv[lane] << 5) | (uint32_t)lane;
+        int rank = 0;
+        for (int q = 0; q < SOFT_WIN; q++) rank += (((uint32_t)sv[q] << 5) | (uint32_t)q) < mine ? 1 : 0;
+        if (rank < L) {
+            cmask[rank] = soft_toggle(lane);
+            csoft[rank] = sv[lane];
+        }
+    }
+    __syncthreads();
+    uint32_t e = 0, w = 0;
+    for (int j = 0; j < L; j++)
+        if ((lane >> j) & 1) e ^= cmask[j], w += csoft[j];
+    int o = -1;
+    if (lane >= 1 && lane < (1 << L)) o = match_block(syn_of(nominal ^ e, pr), expect);
+    uint32_t key = o >= 0 ? (w << 6) | (uint32_t)lane : 0xFFFFFFFFu;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)key, d);
+        key = other < key ? other : key;
+    }
+    __syncthreads();               // cmask and csoft are free for the next judgement
+    if (key == 0xFFFFFFFFu) return 0;
+    const int m = (int)(key & 63u);
+    *m_out = m;
+    *o_out = __shfl(o, m);
+    return (uint32_t)__shfl((int)e, m);
+}
+
+// SOFT: the soft step between the late alignment and the burst table, the call's soft values and the history
+// in LDS (sdr_rds_groups_soft); the default instantiation has none of it
+template <bool SOFT>
 __global__ __launch_bounds__(64) void k_rds_groups(RdsState* __restrict__ st_all, const int32_t* __restrict__ nbits,
                                                    const uint8_t* __restrict__ bits, size_t bits_stride,
                                                    const uint32_t* __restrict__ tab, sdr_rds_group* __restrict__ groups,
-                                                   int32_t* __restrict__ ngroups, int loss_blocks, ParityRows pr) {
+                                                   int32_t* __restrict__ ngroups, int loss_blocks, ParityRows pr,
+                                                   const uint16_t* __restrict__ soft, size_t soft_stride,
+                                                   uint16_t* __restrict__ hist_all, int soft_bits) {
     __shared__ uint64_t wd[6];
     __shared__ uint16_t syn[NWIN];
+    __shared__ uint16_t sv[SOFT ? SOFT_HIST + SDR_MAX_BITS : 1];   // the history, then the call's soft values
+    __shared__ uint32_t cmask[SOFT ? 8 : 1], csoft[SOFT ? 8 : 1];
     const int ch = blockIdx.x, lane = threadIdx.x;
     RdsState* sp = st_all + ch;
     const int nb = nbits[ch];
@@ -114,6 +170,15 @@ __global__ __launch_bounds__(64) void k_rds_groups(RdsState* __restrict__ st_all
     if (lane == 0) {
         wd[0] = 0;
         wd[1] = s.sr;
+    }
+    if constexpr (SOFT) {
+        const uint16_t* srow = soft + (size_t)ch * soft_stride;
+        if (lane < SOFT_HIST) sv[lane] = hist_all[(size_t)ch * SOFT_HIST + lane];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int j = 64 * t + lane;
+            sv[SOFT_HIST + j] = j < nb ? srow[j] : (uint16_t)0;
+        }
     }
     __syncthreads();
     // ---- syndromes of the windows q = lane + 64 t (ending at string position q + 62), hit masks
@@ -154,14 +219,31 @@ __global__ __launch_bounds__(64) void k_rds_groups(RdsState* __restrict__ st_all
                 s.slips++;
             } else {
                 verdict = 2;
-                const int o0 = s.expect == 3 ? 4 : s.expect;
-                fix = tab[(s_nom ^ OFFW[o0]) & 0x3FF];
-                o = o0;
-                if (!fix && s.expect == 2) {
-                    fix = tab[(s_nom ^ OFFW[3]) & 0x3FF];
-                    o = 3;
+                if constexpr (SOFT) {
+                    if (soft_bits > 0) {
+                        // the window's raws i-27 .. i-1 are the call's j-27 .. j-1: sv[HIST + j - 27 ..]
+                        const uint32_t nominal = (uint32_t)tail_bits(wd, j + 1 + 62) & M26;
+                        int so = -1, sm = 0;
+                        fix = soft_search(sv + SOFT_HIST - SOFT_WIN + j, cmask, csoft, nominal, s.expect, soft_bits, pr, lane,
+                                          &so, &sm);
+                        if (fix) {
+                            verdict = 1, corr = 1, o = so;
+                            s.soft_blocks++;
+                            s.soft_flips += (uint32_t)__popc((uint32_t)sm);
+                            s.flags |= (uint8_t)(1u << (SDR_RDS_GROUP_SOFT_SHIFT + s.expect));
+                        }
+                    }
                 }
-                if (fix) verdict = 1, corr = 1;
+                if (!fix) {
+                    const int o0 = s.expect == 3 ? 4 : s.expect;
+                    fix = tab[(s_nom ^ OFFW[o0]) & 0x3FF];
+                    o = o0;
+                    if (!fix && s.expect == 2) {
+                        fix = tab[(s_nom ^ OFFW[3]) & 0x3FF];
+                        o = 3;
+                    }
+                    if (fix) verdict = 1, corr = 1;
+                }
             }
             s.judge_at = next;
             pos = j + 1;
@@ -274,15 +356,20 @@ __global__ __launch_bounds__(64) void k_rds_groups(RdsState* __restrict__ st_all
     // ---- the new history: the 64 bits that end at the call's last bit
     s.sr = tail_bits(wd, 63 + nb);
     s.n = n0 + (uint64_t)nb;
+    if constexpr (SOFT) {          // the soft values of the last bits consumed; nb = 0 rewrites what was there
+        if (lane < SOFT_HIST) hist_all[(size_t)ch * SOFT_HIST + lane] = sv[nb + lane];
+    }
     if (lane == 0) {
         *sp = s;
         ngroups[ch] = ng < SDR_RDS_MAX_GROUPS ? ng : SDR_RDS_MAX_GROUPS;
     }
 }
 
-__global__ void k_rds_reset(RdsState* st, sdr_rds_group* groups, int32_t* ngroups, int nch) {
+__global__ void k_rds_reset(RdsState* st, sdr_rds_group* groups, int32_t* ngroups, int nch, uint16_t* hist) {
     const int ch = blockIdx.x * blockDim.x + threadIdx.x;
     if (ch >= nch) return;
+    if (hist)
+        for (int k = 0; k < SOFT_HIST; k++) hist[(size_t)ch * SOFT_HIST + k] = 0;
     RdsState z;
     memset(&z, 0, sizeof z);
     z.pend_idx = -1;
@@ -300,6 +387,14 @@ __global__ void k_rds_stats(const RdsState* st, sdr_rds_stats* out, int nch) {
     sdr_rds_stats r;
     r.good = s.good, r.corrected = s.ncorrected, r.bad = s.bad, r.slips = s.slips;
     r.acquired = s.acquired, r.lost = s.lost, r.groups = s.groups, r.synced = s.synced;
+    out[ch] = r;
+}
+
+__global__ void k_rds_soft_stats(const RdsState* st, sdr_rds_soft_stats* out, int nch, int soft_bits) {
+    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= nch) return;
+    sdr_rds_soft_stats r;
+    r.soft_blocks = st[ch].soft_blocks, r.soft_flips = st[ch].soft_flips, r.soft_bits = (uint32_t)soft_bits, r.reserved = 0;
     out[ch] = r;
 }
 
@@ -326,7 +421,15 @@ int sdr_rds_mode_ok(int mode) {
     return (long long)in.if_Fs * 247 == 640LL * 2375 * in.symbol_Fs ? 1 : 0;
 }
 
-int sdr_rds_dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opts* opts) {
+void sdr_rds_soft_opts_default(sdr_rds_soft_opts* o) {
+    if (!o) return;
+    o->max_burst = 2;
+    o->loss_blocks = 8;
+    o->soft_bits = 6;
+}
+
+// soft_bits < 0: a handle of sdr_rds_dec_create
+static int dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opts* opts, int soft_bits) {
     if (!out) return fail(SDR_E_INVALID, "rds_dec_create: out is NULL");
     *out = nullptr;
     if (!opts) return fail(SDR_E_INVALID, "rds_dec_create: opts is NULL");
@@ -345,7 +448,11 @@ int sdr_rds_dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opt
     d->nch = nch;
     d->max_burst = opts->max_burst;
     d->loss_blocks = opts->loss_blocks;
+    d->soft = soft_bits >= 0;
+    d->soft_bits = soft_bits >= 0 ? soft_bits : 0;
     hipError_t e = hipMalloc(&d->st, (size_t)nch * sizeof(RdsState));
+    if (e == hipSuccess && d->soft) e = hipMalloc((void**)&d->hist, (size_t)nch * SOFT_HIST * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d->sstats, (size_t)nch * sizeof(sdr_rds_soft_stats));
     if (e == hipSuccess) e = hipMalloc((void**)&d->tab, sizeof tab);
     if (e == hipSuccess) e = hipMalloc((void**)&d->groups, (size_t)nch * SDR_RDS_MAX_GROUPS * sizeof(sdr_rds_group));
     if (e == hipSuccess) e = hipMalloc((void**)&d->ngroups, (size_t)nch * sizeof(int32_t));
@@ -353,7 +460,7 @@ int sdr_rds_dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opt
     if (e == hipSuccess) e = hipMemcpy(d->tab, tab, sizeof tab, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_rds_reset, dim3((nch + 255) / 256), dim3(256), 0, nullptr, (RdsState*)d->st, d->groups,
-                           d->ngroups, nch);
+                           d->ngroups, nch, d->hist);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
@@ -365,6 +472,20 @@ int sdr_rds_dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opt
     return SDR_OK;
 }
 
+int sdr_rds_dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opts* opts) {
+    return dec_create(out, device, nch, opts, -1);
+}
+
+int sdr_rds_dec_create_soft(sdr_rds_dec** out, int device, int nch, const sdr_rds_soft_opts* opts) {
+    if (!out) return fail(SDR_E_INVALID, "rds_dec_create_soft: out is NULL");
+    *out = nullptr;
+    if (!opts) return fail(SDR_E_INVALID, "rds_dec_create_soft: opts is NULL");
+    if (opts->soft_bits < 0 || opts->soft_bits > 6)
+        return fail(SDR_E_INVALID, "rds_dec_create_soft: soft_bits %d is not in 0..6", opts->soft_bits);
+    const sdr_rds_opts ro{opts->max_burst, opts->loss_blocks};
+    return dec_create(out, device, nch, &ro, opts->soft_bits);
+}
+
 int sdr_rds_dec_destroy(sdr_rds_dec* d) {
     if (!d) return fail(SDR_E_INVALID, "rds_dec_destroy: null handle");
     (void)hipSetDevice(d->device);
@@ -374,6 +495,8 @@ int sdr_rds_dec_destroy(sdr_rds_dec* d) {
     if (d->groups) (void)hipFree(d->groups);
     if (d->ngroups) (void)hipFree(d->ngroups);
     if (d->stats) (void)hipFree(d->stats);
+    if (d->hist) (void)hipFree(d->hist);
+    if (d->sstats) (void)hipFree(d->sstats);
     delete d;
     return SDR_OK;
 }
@@ -382,7 +505,7 @@ int sdr_rds_dec_reset(sdr_rds_dec* d, void* stream) {
     if (!d) return fail(SDR_E_INVALID, "rds_dec_reset: null handle");
     HIP_TRY(hipSetDevice(d->device));
     hipLaunchKernelGGL(k_rds_reset, dim3((d->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream, (RdsState*)d->st,
-                       d->groups, d->ngroups, d->nch);
+                       d->groups, d->ngroups, d->nch, d->hist);
     LAUNCH_CHECK();
     return SDR_OK;
 }
@@ -391,10 +514,30 @@ int sdr_rds_groups(sdr_rds_dec* d, const int32_t* nbits_dev, const uint8_t* bits
     if (!d || !nbits_dev || !bits_dev) return fail(SDR_E_INVALID, "rds_groups: null argument");
     if (bits_stride < SDR_MAX_BITS)
         return fail(SDR_E_INVALID, "rds_groups: bits_stride %zu < SDR_MAX_BITS = %d", bits_stride, SDR_MAX_BITS);
+    if (d->soft) return fail(SDR_E_INVALID, "rds_groups: a handle of sdr_rds_dec_create_soft takes sdr_rds_groups_soft");
     HIP_TRY(hipSetDevice(d->device));
     static const ParityRows pr = parity_rows();
-    hipLaunchKernelGGL(k_rds_groups, dim3(d->nch), dim3(64), 0, (hipStream_t)stream, (RdsState*)d->st, nbits_dev, bits_dev,
-                       bits_stride, (const uint32_t*)d->tab, d->groups, d->ngroups, d->loss_blocks, pr);
+    hipLaunchKernelGGL(k_rds_groups<false>, dim3(d->nch), dim3(64), 0, (hipStream_t)stream, (RdsState*)d->st, nbits_dev,
+                       bits_dev, bits_stride, (const uint32_t*)d->tab, d->groups, d->ngroups, d->loss_blocks, pr,
+                       (const uint16_t*)nullptr, (size_t)0, (uint16_t*)nullptr, 0);
+    LAUNCH_CHECK();
+    return SDR_OK;
+}
+
+int sdr_rds_groups_soft(sdr_rds_dec* d, const int32_t* nbits_dev, const uint8_t* bits_dev, size_t bits_stride,
+                        const uint16_t* soft_dev, size_t soft_stride, void* stream) {
+    if (!d || !nbits_dev || !bits_dev || !soft_dev) return fail(SDR_E_INVALID, "rds_groups_soft: null argument");
+    if (bits_stride < SDR_MAX_BITS)
+        return fail(SDR_E_INVALID, "rds_groups_soft: bits_stride %zu < SDR_MAX_BITS = %d", bits_stride, SDR_MAX_BITS);
+    if (soft_stride < SDR_MAX_BITS)
+        return fail(SDR_E_INVALID, "rds_groups_soft: soft_stride %zu < SDR_MAX_BITS = %d", soft_stride, SDR_MAX_BITS);
+    if (reinterpret_cast<uintptr_t>(soft_dev) & 1) return fail(SDR_E_INVALID, "rds_groups_soft: soft_dev is not a uint16 pointer");
+    if (!d->soft) return fail(SDR_E_INVALID, "rds_groups_soft: a handle of sdr_rds_dec_create takes sdr_rds_groups");
+    HIP_TRY(hipSetDevice(d->device));
+    static const ParityRows pr = parity_rows();
+    hipLaunchKernelGGL(k_rds_groups<true>, dim3(d->nch), dim3(64), 0, (hipStream_t)stream, (RdsState*)d->st, nbits_dev,
+                       bits_dev, bits_stride, (const uint32_t*)d->tab, d->groups, d->ngroups, d->loss_blocks, pr, soft_dev,
+                       soft_stride, d->hist, d->soft_bits);
     LAUNCH_CHECK();
     return SDR_OK;
 }
@@ -422,6 +565,18 @@ int sdr_rds_stats_read(sdr_rds_dec* d, sdr_rds_stats* host_stats, void* stream) 
                        d->stats, d->nch);
     LAUNCH_CHECK();
     HIP_TRY(hipMemcpyAsync(host_stats, d->stats, (size_t)d->nch * sizeof(sdr_rds_stats), hipMemcpyDeviceToHost,
+                           (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return SDR_OK;
+}
+
+int sdr_rds_soft_stats_read(sdr_rds_dec* d, sdr_rds_soft_stats* host_stats, void* stream) {
+    if (!d || !host_stats) return fail(SDR_E_INVALID, "rds_soft_stats_read: null argument");
+    HIP_TRY(hipSetDevice(d->device));
+    hipLaunchKernelGGL(k_rds_soft_stats, dim3((d->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       (const RdsState*)d->st, d->sstats, d->nch, d->soft_bits);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(host_stats, d->sstats, (size_t)d->nch * sizeof(sdr_rds_soft_stats), hipMemcpyDeviceToHost,
                            (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return SDR_OK;

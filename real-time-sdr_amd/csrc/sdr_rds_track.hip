@@ -81,10 +81,13 @@ __device__ __forceinline__ void restart(TrackHead& s) {        // back to acquir
     s.level = 0;
 }
 
+// SOFT: the on-time lanes also write |c(t)| >> 6 of their raw decision (sdr_rds_track_bits_soft); the default
+// instantiation has none of it
+template <bool SOFT>
 __global__ __launch_bounds__(64) void k_rds_track(TrackState* __restrict__ st_all, const float* __restrict__ x,
                                                   size_t x_stride, int n, int32_t* __restrict__ nbits,
                                                   uint8_t* __restrict__ bits, size_t bits_stride, int scale_bits,
-                                                  int A, int H_rounds) {
+                                                  int A, int H_rounds, uint16_t* __restrict__ soft, size_t soft_stride) {
     __shared__ int I[TRK_LDS + 4];
     const int ch = blockIdx.x, lane = threadIdx.x;
     TrackState* sp = st_all + ch;
@@ -228,7 +231,10 @@ __global__ __launch_bounds__(64) void k_rds_track(TrackState* __restrict__ st_al
                 if (valid && kind == 1) {
                     const int r = v > 0 ? 1 : 0;
                     const int before = bit == 0 ? s.prev : (int)((raw >> (4 * (bit - 1) + 1)) & 1);
-                    if (nb + bit < SDR_MAX_BITS) bo[nb + bit] = (uint8_t)(r ^ before);
+                    if (nb + bit < SDR_MAX_BITS) {
+                        bo[nb + bit] = (uint8_t)(r ^ before);
+                        if constexpr (SOFT) soft[(size_t)ch * soft_stride + nb + bit] = (uint16_t)(abs(v) >> 6);
+                    }
                 }
                 s.prev = (int)((raw >> (4 * (k - 1) + 1)) & 1);
                 s.early += __shfl(a, 0), s.on += __shfl(a, 1), s.late += __shfl(a, 2), s.half += __shfl(a, 3);
@@ -373,9 +379,15 @@ int sdr_rds_track_reset(sdr_rds_track* t, void* stream) {
     return SDR_OK;
 }
 
-int sdr_rds_track_bits(sdr_rds_track* t, const float* clean_dev, size_t clean_stride, int n, int32_t* nbits_dev,
-                       uint8_t* bits_dev, size_t bits_stride, void* stream) {
+static int track_call(sdr_rds_track* t, const float* clean_dev, size_t clean_stride, int n, int32_t* nbits_dev,
+                      uint8_t* bits_dev, size_t bits_stride, bool with_soft, uint16_t* soft_dev, size_t soft_stride,
+                      void* stream) {
     if (!t || !clean_dev || !nbits_dev || !bits_dev) return fail(SDR_E_INVALID, "rds_track_bits: null argument");
+    if (with_soft && !soft_dev) return fail(SDR_E_INVALID, "rds_track_bits_soft: soft_dev is NULL");
+    if (with_soft && soft_stride < SDR_MAX_BITS)
+        return fail(SDR_E_INVALID, "rds_track_bits_soft: soft_stride %zu < SDR_MAX_BITS = %d", soft_stride, SDR_MAX_BITS);
+    if (with_soft && (reinterpret_cast<uintptr_t>(soft_dev) & 1))
+        return fail(SDR_E_INVALID, "rds_track_bits_soft: soft_dev is not a uint16 pointer");
     if (n < 0 || n > SDR_RDS_TRACK_MAX_N)
         return fail(SDR_E_INVALID, "rds_track_bits: n %d is not in 0..%d (a call holds at most SDR_MAX_BITS bits)", n,
                     SDR_RDS_TRACK_MAX_N);
@@ -388,11 +400,26 @@ int sdr_rds_track_bits(sdr_rds_track* t, const float* clean_dev, size_t clean_st
     int scale_bits;
     std::memcpy(&scale_bits, &scale, sizeof scale_bits);
     // the 16-byte staging path needs every row aligned; the kernel looks at its own row's address
-    hipLaunchKernelGGL(k_rds_track, dim3(t->nch), dim3(64), 0, (hipStream_t)stream, (TrackState*)t->st, clean_dev,
-                       clean_stride, n, nbits_dev, bits_dev, bits_stride, scale_bits, t->opts.acquire_bits,
-                       t->opts.half_bits / SDR_RDS_TRACK_T);
+    if (with_soft)
+        hipLaunchKernelGGL(k_rds_track<true>, dim3(t->nch), dim3(64), 0, (hipStream_t)stream, (TrackState*)t->st, clean_dev,
+                           clean_stride, n, nbits_dev, bits_dev, bits_stride, scale_bits, t->opts.acquire_bits,
+                           t->opts.half_bits / SDR_RDS_TRACK_T, soft_dev, soft_stride);
+    else
+        hipLaunchKernelGGL(k_rds_track<false>, dim3(t->nch), dim3(64), 0, (hipStream_t)stream, (TrackState*)t->st, clean_dev,
+                           clean_stride, n, nbits_dev, bits_dev, bits_stride, scale_bits, t->opts.acquire_bits,
+                           t->opts.half_bits / SDR_RDS_TRACK_T, (uint16_t*)nullptr, (size_t)0);
     LAUNCH_CHECK();
     return SDR_OK;
+}
+
+int sdr_rds_track_bits(sdr_rds_track* t, const float* clean_dev, size_t clean_stride, int n, int32_t* nbits_dev,
+                       uint8_t* bits_dev, size_t bits_stride, void* stream) {
+    return track_call(t, clean_dev, clean_stride, n, nbits_dev, bits_dev, bits_stride, false, nullptr, 0, stream);
+}
+
+int sdr_rds_track_bits_soft(sdr_rds_track* t, const float* clean_dev, size_t clean_stride, int n, int32_t* nbits_dev,
+                            uint8_t* bits_dev, size_t bits_stride, uint16_t* soft_dev, size_t soft_stride, void* stream) {
+    return track_call(t, clean_dev, clean_stride, n, nbits_dev, bits_dev, bits_stride, true, soft_dev, soft_stride, stream);
 }
 
 int sdr_rds_track_stats_read(sdr_rds_track* t, sdr_rds_track_stats* host_stats, void* stream) {

@@ -2,7 +2,7 @@
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
 //   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
-//             [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track]]
+//             [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L]]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //   sdr_multi NCH --wide W [--shift S] --tune FILE ...          (the receiver on wide captures)
 //   sdr_multi NWIDE --wide W [--shift S] --scan ...             (the scan of wide captures)
@@ -45,6 +45,10 @@
 // continuous bit clock and a correlator over the whole bit) instead of the per-block clock recovery (ref, the
 // default); PREFIX.groups and PREFIX.radio are made from them, PREFIX.radio gains a "clock:" line per channel,
 // and PREFIX.rds and every other file stay those of a run without it.
+// --rds-soft L (1-6, with --rds-clock track): soft decisions -- the tracker also writes every bit's reliability and
+// the decoder first searches a failing block over the flips of its L least reliable raw decisions
+// (sdr_rds_groups_soft); in PREFIX.groups a block placed that way ends in "~", PREFIX.radio gains a "soft:" line
+// per channel, and every other file stays that of a run without it.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -64,7 +68,7 @@
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
-                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track]]\n"
+                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L]]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
                          "       sdr_multi NCH --wide W [--shift S] --tune FILE ...   |   sdr_multi NWIDE --wide W [--shift S] --scan ...\n"
@@ -78,6 +82,8 @@ namespace {
                          "            clock time, AF, block error rate per channel); --rds-correct N: bursts up to N bits (0-5, default 2)\n"
                          "  --rds-clock track: the decoder's bits from the symbol tracker (a continuous bit clock, a correlator over\n"
                          "            the whole bit) instead of the per-block clock recovery (ref, default); needs --rds-decode, mode 0\n"
+                         "  --rds-soft L: soft decisions, a failing block is searched over the flips of its L (1-6) least reliable\n"
+                         "            bits before the burst table; needs --rds-clock track\n"
                          "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n"
                          "  --wide W: the input is wide int8 I/Q at W (4, 8, 10) times rf_Fs, rows of 2*W*block_iq bytes, each\n"
                          "            split into 2W-1 capture rows (--shift S: output shift 1-24); needs --tune or --scan\n");
@@ -93,7 +99,7 @@ int main(int argc, char** argv) {
     std::string in = "-", out = "sdr_multi", tune_path;
     if (o.nch <= 0) usage();
     bool scan = false, meter = false, blend = false, finish = false, rds_decode = false, rds_correct = false, rds_clock_set = false;
-    int rds_clock = SDR_MULTI_RDS_CLOCK_REF;
+    int rds_clock = SDR_MULTI_RDS_CLOCK_REF, rds_soft = 0;
     sdr_rds_opts ro{};
     sdr_rds_opts_default(&ro);
     int wide_w = 0, wide_shift = 0;
@@ -142,6 +148,11 @@ int main(int argc, char** argv) {
             else usage();
             rds_clock_set = true;
         }
+        else if (a == "--rds-soft" && i + 1 < argc) {
+            const std::string n = argv[++i];
+            if (n.size() != 1 || n[0] < '1' || n[0] > '6') usage();
+            rds_soft = n[0] - '0';
+        }
         else if (a == "--fast") o.flags |= SDR_FLAG_FAST_FRONTEND;
         else if (a == "--demod" && i + 1 < argc) {
             const std::string d = argv[++i];
@@ -157,6 +168,7 @@ int main(int argc, char** argv) {
     o.out_prefix = out.c_str();
     if (blend && !meter) usage();
     if ((rds_correct || rds_clock_set) && !rds_decode) usage();
+    if (rds_soft && (!rds_decode || rds_clock != SDR_MULTI_RDS_CLOCK_TRACK)) usage();   // only the tracker has reliabilities
     if (rds_decode && (scan || !sdr_rds_mode_ok(o.mode))) usage();   // a scan demodulates nothing; modes 1-3 have no RDS bit clock
     if (wide_shift && !wide_w) usage();
     if (wide_w && !scan && tune_path.empty()) usage();        // a wide run is always tuned
@@ -241,8 +253,9 @@ int main(int argc, char** argv) {
     sdr_meter_opts_default(&mo);
     const sdr_multi_tuning* tp = tune_path.empty() ? nullptr : &tune;
     const sdr_multi_rds rd{ro.max_burst, ro.loss_blocks};
-    const int rc = rds_decode ? sdr_multi_run_rds_clock(&o, wide_w ? &wd : nullptr, tp, meter ? &mo : nullptr, finish ? &ao : nullptr,
-                                                        blend ? 1 : 0, &rd, rds_clock, nullptr, &st)
+    const sdr_rds_soft_opts sq{ro.max_burst, ro.loss_blocks, rds_soft};
+    const int rc = rds_decode ? sdr_multi_run_rds_soft(&o, wide_w ? &wd : nullptr, tp, meter ? &mo : nullptr, finish ? &ao : nullptr,
+                                                       blend ? 1 : 0, &rd, rds_clock, nullptr, rds_soft ? &sq : nullptr, &st)
                    : wide_w ? sdr_multi_run_wide(&o, &wd, tp, meter ? &mo : nullptr, finish ? &ao : nullptr, blend ? 1 : 0, &st)
                    : finish ? sdr_multi_run_finished(&o, tp, meter ? &mo : nullptr, &ao, blend ? 1 : 0, &st)
                    : meter ? sdr_multi_run_metered(&o, tp, &mo, &st)

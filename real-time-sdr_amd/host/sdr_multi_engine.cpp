@@ -103,6 +103,7 @@ struct RunSpec {
     const sdr_multi_rds* rds = nullptr;       // the RDS group decoder (sdr_multi_run_rds)
     int rds_clock = SDR_MULTI_RDS_CLOCK_REF;  //   whose bits it reads (sdr_multi_run_rds_clock)
     const sdr_rds_track_opts* track = nullptr;   // the tracker's options, with SDR_MULTI_RDS_CLOCK_TRACK
+    const sdr_rds_soft_opts* soft = nullptr;  // soft decisions on the tracker's clock (sdr_multi_run_rds_soft)
 };
 
 // Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused.
@@ -123,6 +124,11 @@ bool validate(const RunSpec& r) {
         if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds || !t) return false;
         if (t->qshift < 0 || t->qshift > 15 || t->acquire_bits < 1 || t->acquire_bits > 64 || t->half_bits < SDR_RDS_TRACK_T ||
             t->half_bits > 64 || t->half_bits % SDR_RDS_TRACK_T)
+            return false;
+    }
+    if (const sdr_rds_soft_opts* q = r.soft) {   // only the tracker has reliabilities; what sdr_rds_dec_create_soft would refuse
+        if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds) return false;
+        if (q->max_burst < 0 || q->max_burst > 5 || q->loss_blocks < 1 || q->loss_blocks > 64 || q->soft_bits < 0 || q->soft_bits > 6)
             return false;
     }
     if (const sdr_multi_tuning* t = r.tune) {   // the tuning's bounds (sdr_tuner_set's)
@@ -414,7 +420,10 @@ struct RdsRes {
     sdr_rds_track* trk = nullptr;
     DevBuf<int32_t> d_tnbits;
     DevBuf<uint8_t> d_tbits;
-    RdsRes(const sdr_multi_opts& o, const sdr_multi_rds* rds, const sdr_rds_track_opts* track, bool cache) {
+    // ... with soft decisions (sdr_multi_run_rds_soft): the tracker's reliabilities of those bits
+    DevBuf<uint16_t> d_tsoft;
+    RdsRes(const sdr_multi_opts& o, const sdr_multi_rds* rds, const sdr_rds_track_opts* track, const sdr_rds_soft_opts* soft,
+           bool cache) {
         const int nch = o.nch;
         pre.make();
         pll.make();
@@ -427,7 +436,8 @@ struct RdsRes {
         }
         if (!rds) return;
         const sdr_rds_opts ro{rds->max_burst, rds->loss_blocks};
-        check_sdr(sdr_rds_dec_create(&dec, o.device, nch, &ro), "sdr_rds_dec_create");
+        if (soft) check_sdr(sdr_rds_dec_create_soft(&dec, o.device, nch, soft), "sdr_rds_dec_create_soft");
+        else check_sdr(sdr_rds_dec_create(&dec, o.device, nch, &ro), "sdr_rds_dec_create");
         for (int h = 0; h < NH; h++) {
             h_groups[h].take((size_t)nch * SDR_RDS_MAX_GROUPS * sizeof(sdr_rds_group), cache);
             h_ngroups[h].take(nch * sizeof(int32_t), cache);
@@ -436,6 +446,7 @@ struct RdsRes {
         check_sdr(sdr_rds_track_create(&trk, o.device, nch, o.mode, track), "sdr_rds_track_create");
         d_tnbits.get((size_t)nch);
         d_tbits.get((size_t)nch * SDR_MAX_BITS);
+        if (soft) d_tsoft.get((size_t)nch * SDR_MAX_BITS);
     }
     ~RdsRes() {
         if (trk) (void)sdr_rds_track_destroy(trk);
@@ -925,13 +936,20 @@ void rds_thread(Shared* sh) {
             size_t clean_stride = 0;
             int n_rds = 0;
             check_sdr(sdr_ctx_buffer(ctx, "rds_clean", &clean, &clean_stride, &n_rds), "sdr_ctx_buffer");
-            check_sdr(sdr_rds_track_bits(r.trk, clean, clean_stride, n_rds, r.d_tnbits.p, r.d_tbits.p, SDR_MAX_BITS, s),
-                      "sdr_rds_track_bits");
+            if (r.d_tsoft.p)
+                check_sdr(sdr_rds_track_bits_soft(r.trk, clean, clean_stride, n_rds, r.d_tnbits.p, r.d_tbits.p, SDR_MAX_BITS,
+                                                  r.d_tsoft.p, SDR_MAX_BITS, s),
+                          "sdr_rds_track_bits_soft");
+            else
+                check_sdr(sdr_rds_track_bits(r.trk, clean, clean_stride, n_rds, r.d_tnbits.p, r.d_tbits.p, SDR_MAX_BITS, s),
+                          "sdr_rds_track_bits");
         }
         if (r.dec) {   // on the bits where they are; the last block's stream follows the others' (consumer_pll)
             const int32_t* nbits = r.trk ? r.d_tnbits.p : r.d_nbits.p;
             const uint8_t* bits = r.trk ? r.d_tbits.p : r.d_bits.p;
-            check_sdr(sdr_rds_groups(r.dec, nbits, bits, SDR_MAX_BITS, s), "sdr_rds_groups");
+            if (r.d_tsoft.p)
+                check_sdr(sdr_rds_groups_soft(r.dec, nbits, bits, SDR_MAX_BITS, r.d_tsoft.p, SDR_MAX_BITS, s), "sdr_rds_groups_soft");
+            else check_sdr(sdr_rds_groups(r.dec, nbits, bits, SDR_MAX_BITS, s), "sdr_rds_groups");
             check_sdr(sdr_rds_groups_copy(r.dec, r.h_groups[k], r.h_ngroups[k], s), "sdr_rds_groups_copy");
         }
         check_hip(hipEventRecord(r.out_ready[k], s), "hipEventRecord");
@@ -958,7 +976,9 @@ void rds_thread(Shared* sh) {
                     std::fprintf(groups, "ch %d bits %u", c, g.bits);
                     for (int w = 0; w < 4; w++) {
                         if (!((g.ok >> w) & 1)) std::fprintf(groups, " ----");
-                        else std::fprintf(groups, " %04X%s", g.w[w], ((g.corrected >> w) & 1) ? "*" : "");
+                        else   // a block the soft step placed ends in "~", one the burst table corrected in "*"
+                            std::fprintf(groups, " %04X%s", g.w[w],
+                                         ((g.flags >> (SDR_RDS_GROUP_SOFT_SHIFT + w)) & 1) ? "~" : ((g.corrected >> w) & 1) ? "*" : "");
                     }
                     std::fprintf(groups, "\n");
                 }
@@ -992,6 +1012,8 @@ void rds_thread(Shared* sh) {
         check_sdr(sdr_rds_stats_read(r.dec, stats.data(), sh->s_post_c[1]), "sdr_rds_stats_read");
         std::vector<sdr_rds_track_stats> clock(r.trk ? (size_t)o.nch : 0);
         if (r.trk) check_sdr(sdr_rds_track_stats_read(r.trk, clock.data(), sh->s_post_c[1]), "sdr_rds_track_stats_read");
+        std::vector<sdr_rds_soft_stats> soft(r.d_tsoft.p ? (size_t)o.nch : 0);
+        if (r.d_tsoft.p) check_sdr(sdr_rds_soft_stats_read(r.dec, soft.data(), sh->s_post_c[1]), "sdr_rds_soft_stats_read");
         File radio;
         radio.open(std::string(o.out_prefix) + ".radio", "w");
         std::vector<char> buf(4096);
@@ -1004,6 +1026,8 @@ void rds_thread(Shared* sh) {
             const sdr_rds_track_stats& k = clock[(size_t)c];
             std::fprintf(radio, "ch %d: clock: locked %u phase %u bits %u moves %u half_moves %u resets %u level %u\n", c, k.locked,
                          k.phase, k.bits, k.moves, k.half_moves, k.resets, k.level);
+            if (r.d_tsoft.p)
+                std::fprintf(radio, "ch %d: soft: blocks %u flips %u\n", c, soft[(size_t)c].soft_blocks, soft[(size_t)c].soft_flips);
         }
     }
     File f;
@@ -1094,7 +1118,7 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     mark("streams");
     const size_t lr_bytes = 2 * (size_t)sh.info.n_audio * o.nch * sizeof(int16_t);
     sh.ar.emplace(lr_bytes, sw.pin_cache);
-    sh.rr.emplace(o, spec.rds, spec.rds_clock == SDR_MULTI_RDS_CLOCK_TRACK ? spec.track : nullptr, sw.pin_cache);
+    sh.rr.emplace(o, spec.rds, spec.rds_clock == SDR_MULTI_RDS_CLOCK_TRACK ? spec.track : nullptr, spec.soft, sw.pin_cache);
     if (spec.meter) sh.meter.emplace(o, *spec.meter, sw.pin_cache);
     if (spec.audio) sh.fin.emplace(o, *spec.audio, spec.blend, lr_bytes, sw.pin_cache);
     mark("consumer buffers");
@@ -1200,9 +1224,19 @@ extern "C" int sdr_multi_run_rds(const sdr_multi_opts* opts, const sdr_multi_wid
 extern "C" int sdr_multi_run_rds_clock(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
                                        const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, const sdr_multi_rds* rds,
                                        int rds_clock, const sdr_rds_track_opts* track, sdr_multi_stats* stats) {
-    if (rds_clock == SDR_MULTI_RDS_CLOCK_REF) return sdr_multi_run_rds(opts, wide, tune, mo, ao, blend, rds, stats);
+    return sdr_multi_run_rds_soft(opts, wide, tune, mo, ao, blend, rds, rds_clock, track, nullptr, stats);
+}
+
+extern "C" int sdr_multi_run_rds_soft(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
+                                      const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, const sdr_multi_rds* rds,
+                                      int rds_clock, const sdr_rds_track_opts* track, const sdr_rds_soft_opts* soft,
+                                      sdr_multi_stats* stats) {
+    if (rds_clock == SDR_MULTI_RDS_CLOCK_REF) {
+        if (soft) return SDR_E_INVALID;   // the reference clock has no reliabilities
+        return sdr_multi_run_rds(opts, wide, tune, mo, ao, blend, rds, stats);
+    }
     if (!rds || (wide && !tune)) return SDR_E_INVALID;
     sdr_rds_track_opts defaults;
     sdr_rds_track_opts_default(&defaults);
-    return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, rds_clock, track ? track : &defaults}, stats);
+    return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, rds_clock, track ? track : &defaults, soft}, stats);
 }
