@@ -15,7 +15,8 @@ LIB      := $(PKG)/libsdr_amd.so
 SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_ctx.hip $(PKG)/csrc/sdr_plls.cpp $(PKG)/csrc/sdr_streams.hip \
             $(PKG)/csrc/sdr_primitives.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_scan.hip \
             $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip $(PKG)/csrc/sdr_split.hip \
-            $(PKG)/csrc/sdr_rds.hip $(PKG)/csrc/sdr_rds_track.hip $(PKG)/csrc/sdr_taps.cpp $(PKG)/csrc/sdr_rds_text.cpp
+            $(PKG)/csrc/sdr_rds.hip $(PKG)/csrc/sdr_rds_track.hip $(PKG)/csrc/sdr_rds_carrier.hip \
+            $(PKG)/csrc/sdr_taps.cpp $(PKG)/csrc/sdr_rds_text.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
 HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h $(PKG)/csrc/demod_phase.h \
             $(PKG)/csrc/nco.h $(PKG)/csrc/stage_device.h

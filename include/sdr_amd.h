@@ -50,6 +50,8 @@ extern "C" {
                                           * resamplers are fused and only the rows' history is stored */
 #define SDR_FLAG_PHASE_DEMOD 0x8    /* phase discriminator (below): fm_demod is the phase step in radians,
                                      * not its sine; not with SDR_FLAG_FAST_FRONTEND (SDR_E_INVALID) */
+#define SDR_FLAG_RDS_QUAD 0x10      /* sdr_rds_post also runs the RDS chain's quadrature branch (below, at
+                                     * sdr_ctx_rds_clean_q); mode 0 with rds_on only (SDR_E_INVALID) */
 
 /* ---- phase discriminator (no reference counterpart; sdr_version stays 3, callers detect it by symbol).
  * fmDemodNoArctan's value is Im(x[n] conj(x[n-1])) / |x[n]|^2 = (|x[n-1]| / |x[n]|) sin(dphi): the sine of
@@ -674,6 +676,71 @@ int sdr_rds_groups_soft(sdr_rds_dec *d, const int32_t *nbits_dev, const uint8_t 
 /* host [nch]; synchronises `stream`; a handle of sdr_rds_dec_create reads as zeros */
 int sdr_rds_soft_stats_read(sdr_rds_dec *d, sdr_rds_soft_stats *host_stats, void *stream);
 
+/* ---- RDS carrier-phase derotator (no reference counterpart; callers detect it by symbol): the reference's
+ * RDS chain demodulates with a carrier that sits at an unexplained, roughly constant angle (about 45 degrees)
+ * off the 57 kHz subcarrier, so its rds_clean row holds only part of the RDS power. Given that row and the same
+ * chain run with the quadrature carrier, this stage estimates the angle from the squared signal, window by
+ * window, and turns both rows onto one axis: out = Re((I + jQ) e^{-j phi}), rows the tracker reads as it reads
+ * rds_clean. Mode 0 only (sdr_rds_mode_ok). One quantisation, then all integer: no libm and no floating point
+ * after it; tests/rds_carrier_model.py defines every bit, DESIGN.md section 4j explains the constants.
+ * Per channel, with t the index of a sample in the stream since the last reset or poisoned call:
+ *   quantise   qi, qq = rint(clamp(x * 2^qshift, +-32767)) of the two rows, as the tracker quantises
+ *   rotate     y = clamp((qi c + qq s + 2^13) >> 14, +-32767), out = y * 2^-qshift as f32, which is exact: the
+ *              tracker's own quantisation (same qshift) gets y back. |qi c + qq s| <= 32767 * 23173 < 2^31.
+ *   window     (c, s) is constant over a window of SDR_RDS_CARRIER_W samples of the stream (not of the call)
+ *              and (2^14, 0) in the first one
+ *   phasor     at the end of a window: Pr = sum(qi^2 - qq^2), Pi = sum(2 qi qq), Pt = sum(qi^2 + qq^2) over
+ *              its samples, int64: a term is below 2^31, a sum at most W * 2^31 = 2^42. Then
+ *              Sr += (Pr - Sr) >> avg_shift, Si and St likewise, the shift arithmetic: S stays between its old
+ *              value and P, so |S| <= 2^42 too.
+ *   angle      with m = max(|Sr|, |Si|) > 0, Sr and Si are shifted by the same count, right (arithmetic) or
+ *              left, that puts m into [2^28, 2^29). A vectoring CORDIC of SDR_RDS_CARRIER_CORDIC_N = 24
+ *              iterations on int32 gives the angle of (x, y), an int32 with a turn = 2^32:
+ *                z = 0; x < 0: (x, y, z) = (-x, -y, 2^31)
+ *                i = 0 .. 23:  y >= 0: (x, y, z) = (x + (y >> i), y - (x >> i), z + A[i])
+ *                              else:   (x, y, z) = (x - (y >> i), y + (x >> i), z - A[i])
+ *              A[i] = round(atan(2^-i) / 2 pi * 2^32) = 536870912, 316933406, 167458907, 85004756, 42667331,
+ *              21354465, 10679838, 5340245, 2670163, 1335087, 667544, 333772, 166886, 83443, 41722, 20861,
+ *              10430, 5215, 2608, 1304, 652, 326, 163, 81. (x grows by 1.6468: below 2^29.5 * 1.6468 < 2^31.)
+ *              phi = z >> 1 (arithmetic); if |wrap32(phi - phi_prev)| > 2^30, phi += 2^31 (wrapping): of the
+ *              two answers half a turn apart, the one nearer the last. m = 0 keeps phi and (c, s).
+ *   vector     (c, s) of the next window by the rotation CORDIC: z = phi; |z| > 2^30: z -= 2^31 (wrapping) and
+ *              the result is negated; (x, y) = (326016437, 0) (2^29 over the CORDIC's gain);
+ *                i = 0 .. 23:  z >= 0: (x, y, z) = (x - (y >> i), y + (x >> i), z - A[i])
+ *                              else:   (x, y, z) = (x + (y >> i), y - (x >> i), z + A[i])
+ *              c = (x + 2^14) >> 15, s = (y + 2^14) >> 15.
+ *   state      the partial sums and length of the current window, S, phi, (c, s), the counters. No samples.
+ * A call: n = 0 is legal and changes nothing. A non-finite sample in either row within the channel's n writes
+ * NaN to all n samples of its output row (the tracker behind it then reports SDR_NBITS_POISONED), uses none of
+ * the call's samples and puts the channel back to its first window (phi = 0, S = 0; resets + 1, windows
+ * stays). The result does not depend on how a channel's stream is cut into calls. The output rows must not
+ * overlap the input rows.
+ * SDR_E_INVALID, nothing enqueued: NULL handles or pointers, nch < 1, a mode sdr_rds_mode_ok refuses, options
+ * out of range, n < 0 or > SDR_RDS_TRACK_MAX_N, a stride < n, a pointer that is not a float's. */
+#define SDR_RDS_CARRIER_W 2048        /* samples of the stream per window */
+#define SDR_RDS_CARRIER_CORDIC_N 24
+typedef struct sdr_rds_carrier_stats {   /* 40 bytes */
+    int64_t sr, si, st;           /* the smoothed phasor of the squared signal and the smoothed power */
+    int32_t phi;                  /* the phase in use, a turn = 2^32: degrees = phi * 360 / 2^32 */
+    uint32_t windows;             /* windows completed since the last reset */
+    uint32_t resets;              /* poisoned calls */
+    uint32_t reserved;            /* 0 */
+} sdr_rds_carrier_stats;          /* coherence = hypot(sr, si) / st: 1 for a clean BPSK subcarrier, near 0 for noise */
+typedef struct sdr_rds_carrier_opts {
+    int qshift;                   /* 0..15; the tracker behind it wants the same */
+    int avg_shift;                /* 0..6: S += (P - S) >> avg_shift */
+} sdr_rds_carrier_opts;
+void sdr_rds_carrier_opts_default(sdr_rds_carrier_opts *o);   /* 10, 3 */
+typedef struct sdr_rds_carrier sdr_rds_carrier;
+int sdr_rds_carrier_create(sdr_rds_carrier **out, int device, int nch, int mode, const sdr_rds_carrier_opts *opts);
+int sdr_rds_carrier_destroy(sdr_rds_carrier *h);
+int sdr_rds_carrier_reset(sdr_rds_carrier *h, void *stream);
+/* one kernel (one wave per channel) on `stream`: clean_i, clean_q [nch][stride] f32 in, out [nch][out_stride] */
+int sdr_rds_carrier_rotate(sdr_rds_carrier *h, const float *clean_i, size_t stride_i, const float *clean_q,
+                           size_t stride_q, int n, float *out, size_t out_stride, void *stream);
+/* host [nch]; synchronises `stream` */
+int sdr_rds_carrier_stats_read(sdr_rds_carrier *h, sdr_rds_carrier_stats *host_stats, void *stream);
+
 /* mono loop body (mono.cpp:34-42) on the current block: audio [nch][n_audio] int16 */
 int sdr_mono(sdr_ctx *ctx, int16_t *audio, size_t audio_stride, void *stream);
 /* stereo loop body (stereo.cpp:74-107): lr [nch][2*n_audio] int16, L/R interleaved */
@@ -793,6 +860,22 @@ int sdr_get_fm_demod(sdr_ctx *ctx, float *fm, size_t fm_stride, void *stream);
  * with SDR_FLAG_KEEP_INTERMEDIATES): name in {"fm","pilot","carrier","band","rds_band",
  * "gen_pilot","ipll","rds_dc","rds_filt","rds_clean","stereo_dc"}; *stride in elements. */
 int sdr_ctx_buffer(sdr_ctx *ctx, const char *name, const float **ptr, size_t *stride, int *len);
+
+/* ---- RDS quadrature branch (no reference counterpart; callers detect it by symbol). With SDR_FLAG_RDS_QUAD,
+ * sdr_rds_post runs the reference's RDS chain from the mixer on a second time, with the quadrature of its
+ * carrier, into rds_clean_q [nch][n_rds]; every other result of the context stays bit for bit what it is
+ * without the flag. Per block of n = block_if samples, t[] the 114 kHz PLL's phases of the block:
+ *     ipll_q[i]   = RN32(cos((double)(t[i-1] * 0.5f + -(float)(pi/2)))), i = 1 .. n: the reference's NCO output
+ *                   (pll.cpp:52) with phaseAdjust -pi/2; ipll_q[0] is the previous block's ipll_q[n], and
+ *                   0.0f in the first block and after sdr_ctx_reset
+ *     rds_dc_q[i] = (2 * (rds_band[i - 50] + 0)) * ipll_q[i], i = 0 .. n-1, in f32 (rds.cpp:122-127)
+ *     rds_filt_q  = the 247/640 resampler of rds.cpp:130 over rds_dc_q, rds_clean_q = the RRC of :133 over it,
+ *                   with FIR states of their own (zero at the start)
+ * which is fmpll(gen_pilot, 114e3, if_Fs, out_q, st_q, 0.5, -(float)(pi/2), 0.001) on a pllblock_args and a
+ * zeroed out_q of its own, then the reference's mixer, resampler and RRC. A poisoned block (SDR_NBITS_POISONED
+ * above) writes NaN rows to rds_clean_q as to rds_clean. The rows are also "rds_clean_q", "rds_filt_q" and
+ * "rds_dc_q" of sdr_ctx_buffer. SDR_E_INVALID without the flag. */
+int sdr_ctx_rds_clean_q(sdr_ctx *ctx, const float **ptr, size_t *stride, int *len);
 
 /* Streams on disjoint CU sets (no reference counterpart: the reference's three threads,
  * project.cpp:134-136, share one CPU; this is their placement on the GPU). Creates a HIP stream

@@ -72,6 +72,22 @@ int sdr_multi_run_rds_soft(const sdr_multi_opts *opts, const sdr_multi_wide *wid
                            int rds_clock, const sdr_rds_track_opts *track, const sdr_rds_soft_opts *soft,
                            sdr_multi_stats *stats);
 
+/* sdr_multi_run_rds_soft on coherent rows (the CLI's --rds-carrier quad); carrier == NULL is that call. With
+ * carrier the RDS thread's context is created with SDR_FLAG_RDS_QUAD, and behind the block's RRCs on its post
+ * stream the thread runs sdr_rds_carrier_rotate (include/sdr_amd.h, sdr_rds_carrier_*) on the context's rds_clean
+ * and rds_clean_q rows into one more [nch][n_rds] f32 row set of the engine's pool, then the tracker on those
+ * rows in place of rds_clean, then the decoder. PREFIX.groups and PREFIX.radio are made from the new bits, and
+ * PREFIX.radio gains, directly behind every channel's clock line (before a soft line), the line
+ *   ch <c>: carrier: phase <degrees, %.2f> coherence <hypot(sr, si) / st, %.3f> windows <n> resets <r>
+ * of its sdr_rds_carrier_stats. PREFIX.rds, the PCM, the captures and every other file are byte for byte those
+ * of the run without carrier: sdr_rds_bits still reads rds_clean.
+ * SDR_E_INVALID, before anything starts, also for carrier without SDR_MULTI_RDS_CLOCK_TRACK or without rds, and
+ * for carrier options out of range (qshift 0..15, avg_shift 0..6). */
+int sdr_multi_run_rds_carrier(const sdr_multi_opts *opts, const sdr_multi_wide *wide, const sdr_multi_tuning *tune,
+                              const sdr_meter_opts *mo, const sdr_audio_opts *ao, int blend, const sdr_multi_rds *rds,
+                              int rds_clock, const sdr_rds_track_opts *track, const sdr_rds_soft_opts *soft,
+                              const sdr_rds_carrier_opts *carrier, sdr_multi_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ FLAG_FAST_FRONTEND = 0x1
 FLAG_PLL_LIBM = 0x2
 FLAG_KEEP_INTERMEDIATES = 0x4
 PHASE_DEMOD = FLAG_PHASE_DEMOD = 0x8   # fm_demod is the phase step in radians (include/sdr_amd.h); not with FAST
+RDS_QUAD = FLAG_RDS_QUAD = 0x10        # rds / rds_post also run the RDS chain's quadrature branch (Pipeline.rds_clean_q)
 
 _lib = None
 
@@ -128,6 +129,17 @@ class RdsTrackOpts(C.Structure):
     _fields_ = [("qshift", C.c_int), ("acquire_bits", C.c_int), ("half_bits", C.c_int)]
 
 
+class RdsCarrierStats(C.Structure):
+    """sdr_rds_carrier_stats: one channel's carrier phase and smoothed sums, 40 bytes."""
+    _fields_ = [("sr", C.c_int64), ("si", C.c_int64), ("st", C.c_int64), ("phi", C.c_int32), ("windows", C.c_uint32),
+                ("resets", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RdsCarrierOpts(C.Structure):
+    """sdr_rds_carrier_opts: the quantisation shift and the shift of the phasor's smoothing."""
+    _fields_ = [("qshift", C.c_int), ("avg_shift", C.c_int)]
+
+
 class RdsSoftOpts(C.Structure):
     """sdr_rds_soft_opts: sdr_rds_opts and the number of least reliable raw decisions the soft step may flip."""
     _fields_ = [("max_burst", C.c_int), ("loss_blocks", C.c_int), ("soft_bits", C.c_int)]
@@ -141,6 +153,7 @@ class RdsSoftStats(C.Structure):
 RDS_MAX_GROUPS = 4
 RDS_GROUP_SOFT_SHIFT, RDS_SOFT_HISTORY = 4, 32
 RDS_TRACK_T, RDS_TRACK_CARRY, RDS_TRACK_MAX_N = 16, 120, 19712
+RDS_CARRIER_W, RDS_CARRIER_CORDIC_N = 2048, 24
 RDS_GROUP_CPRIME = 0x1
 METER_ROW_AUDIO, METER_ROW_RDS = 0x1, 0x2                                   # MeterRow.flags
 METER_STEREO, METER_RDS, METER_OFFTUNE, METER_DEAD_AIR = 0x1, 0x2, 0x4, 0x8   # MeterState.flags
@@ -211,6 +224,7 @@ def lib() -> C.CDLL:
         "sdr_plls_timeline": ([vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), i32, C.POINTER(i32), vp], i32),
         "sdr_rds_post": ([vp, vp, sz, vp], i32),
         "sdr_ctx_buffer": ([vp, C.c_char_p, C.POINTER(vp), C.POINTER(sz), C.POINTER(i32)], i32),
+        "sdr_ctx_rds_clean_q": ([vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(i32)], i32),
         "sdr_hbm_copy": ([vp, vp, sz, vp], i32),
         "sdr_scan_geometry": ([i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], i32),
         "sdr_scan_window": ([i32, vp, i32, C.POINTER(i32)], i32),
@@ -269,6 +283,12 @@ def lib() -> C.CDLL:
         "sdr_rds_track_reset": ([vp, vp], i32),
         "sdr_rds_track_bits": ([vp, vp, sz, i32, vp, vp, sz, vp], i32),
         "sdr_rds_track_stats_read": ([vp, vp, vp], i32),
+        "sdr_rds_carrier_opts_default": ([C.POINTER(RdsCarrierOpts)], None),
+        "sdr_rds_carrier_create": ([C.POINTER(vp), i32, i32, i32, C.POINTER(RdsCarrierOpts)], i32),
+        "sdr_rds_carrier_destroy": ([vp], i32),
+        "sdr_rds_carrier_reset": ([vp, vp], i32),
+        "sdr_rds_carrier_rotate": ([vp, vp, sz, vp, sz, i32, vp, sz, vp], i32),
+        "sdr_rds_carrier_stats_read": ([vp, vp, vp], i32),
         "sdr_rds_station_init": ([C.POINTER(RdsStationC)], None),
         "sdr_rds_station_update": ([C.POINTER(RdsStationC), C.POINTER(RdsGroup)], None),
         "sdr_rds_station_stats": ([C.POINTER(RdsStationC), C.POINTER(RdsStats)], None),
@@ -986,6 +1006,114 @@ class RdsTracker:
         return out
 
 
+def rds_carrier_stats_dtype():
+    """numpy dtype of sdr_rds_carrier_stats (40 bytes)."""
+    import numpy as np
+    return np.dtype(RdsCarrierStats)
+
+
+def rds_carrier_opts(**opts) -> RdsCarrierOpts:
+    """The derotator's defaults (sdr_rds_carrier_opts_default) with the given fields replaced."""
+    o = RdsCarrierOpts()
+    lib().sdr_rds_carrier_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(RdsCarrierOpts._fields_):
+            raise SdrError(f"rds_carrier_opts: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+def rds_carrier_phase_deg(stats):
+    """The phase in use in degrees, of records of rds_carrier_stats_dtype()."""
+    import numpy as np
+    return np.asarray(stats["phi"], np.float64) * (360.0 / 2.0 ** 32)
+
+
+def rds_carrier_coherence(stats):
+    """hypot(sr, si) / st of records of rds_carrier_stats_dtype(): 1 for a clean BPSK subcarrier, near 0 for
+    noise, 0 before the first window."""
+    import numpy as np
+    st = np.asarray(stats["st"], np.float64)
+    h = np.hypot(np.asarray(stats["sr"], np.float64), np.asarray(stats["si"], np.float64))
+    return np.divide(h, st, out=np.zeros_like(h), where=st > 0)
+
+
+class RdsCarrier:
+    """The RDS carrier-phase derotator of `nch` channels (sdr_rds_carrier_*): per call it turns the in-phase and
+    quadrature rds_clean rows onto one axis by the phase of their squared signal, estimated window by window of
+    the stream, on the GPU. feed(clean_i, clean_q) returns rows that RdsTracker.feed takes in place of rds_clean.
+    Mode 0 only. Its own handle; the state stays on the device."""
+
+    def __init__(self, nch: int, device: int = 0, mode: int = 0, **opts):
+        h = C.c_void_p()
+        o = rds_carrier_opts(**opts)
+        check(lib().sdr_rds_carrier_create(C.byref(h), device, nch, mode, C.byref(o)), "sdr_rds_carrier_create")
+        self._h = h
+        self.nch, self.device = nch, device
+        self.out = None                  # the rotated rows, allocated by the first feed() that is given none
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sdr_rds_carrier_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().sdr_rds_carrier_reset(self._h, _stream(stream)), "sdr_rds_carrier_reset")
+
+    def feed(self, clean_i, clean_q, n: int | None = None, stream=None, out=None):
+        """One call: clean_i and clean_q are float32 [nch][>= n] device tensors (n: the shorter row length by
+        default); returns the rotated rows, float32 [nch][>= n]: `out`, or the handle's own tensor, which the
+        next call overwrites."""
+        import torch
+        for name, x in (("clean_i", clean_i), ("clean_q", clean_q)):
+            if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.nch:
+                raise ValueError(f"{name} must be a float32 [{self.nch}][n] tensor")
+        n = int(min(clean_i.shape[1], clean_q.shape[1])) if n is None else int(n)
+        if n > min(clean_i.shape[1], clean_q.shape[1]):
+            raise ValueError(f"n {n} > a row's length")
+        if out is None:
+            if self.out is None or self.out.shape[1] < n:
+                self.out = torch.zeros(self.nch, max(n, 1), dtype=torch.float32, device=clean_i.device)
+            out = self.out
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != self.nch or out.shape[1] < n:
+            raise ValueError(f"out must be a float32 [{self.nch}][>= {n}] tensor")
+        check(lib().sdr_rds_carrier_rotate(self._h, _ptr(clean_i), _row_stride(clean_i), _ptr(clean_q), _row_stride(clean_q),
+                                           n, _ptr(out), _row_stride(out), _stream(stream)), "sdr_rds_carrier_rotate")
+        return out
+
+    def feed_pipeline(self, pipe: "Pipeline", clean, stream=None, out=None):
+        """The rds_clean rows a RDS_QUAD pipeline's rds() or rds_post() of the current block returned, with the
+        context's own rds_clean_q rows where they are (same stream, no copy); returns the rotated rows."""
+        import torch
+        p, s, n = C.c_void_p(), C.c_size_t(), C.c_int()
+        check(lib().sdr_ctx_rds_clean_q(pipe._h, C.byref(p), C.byref(s), C.byref(n)), "sdr_ctx_rds_clean_q")
+        if clean.dtype != torch.float32 or clean.dim() != 2 or clean.shape[0] != self.nch or clean.shape[1] < n.value:
+            raise ValueError(f"clean must be a float32 [{self.nch}][>= {n.value}] tensor")
+        if out is None:
+            if self.out is None or self.out.shape[1] < n.value:
+                self.out = torch.zeros(self.nch, n.value, dtype=torch.float32, device=clean.device)
+            out = self.out
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != self.nch or out.shape[1] < n.value:
+            raise ValueError(f"out must be a float32 [{self.nch}][>= {n.value}] tensor")
+        check(lib().sdr_rds_carrier_rotate(self._h, _ptr(clean), _row_stride(clean), p, s.value, n.value, _ptr(out),
+                                           _row_stride(out), _stream(stream)), "sdr_rds_carrier_rotate")
+        return out
+
+    def stats(self, stream=None):
+        """numpy structured array [nch] of rds_carrier_stats_dtype(); synchronises the stream."""
+        import numpy as np
+        out = np.zeros(self.nch, rds_carrier_stats_dtype())
+        check(lib().sdr_rds_carrier_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)),
+              "sdr_rds_carrier_stats_read")
+        return out
+
+
 class RdsStation:
     """The text layer of one station (sdr_rds_station_*, host only): update(groups) with records of
     rds_group_dtype(), text() for the report; the fields are on .s (RdsStationC)."""
@@ -1347,6 +1475,25 @@ class Pipeline:
             check(lib().sdr_rds_bits(self._h, _ptr(self.offset), _ptr(self.nsym), _ptr(self.symbols),
                                      SDR_MAX_SYMS, _ptr(self.nbits), _ptr(self.bits), SDR_MAX_BITS,
                                      _stream(stream)), "sdr_rds_bits")
+        return out
+
+    def rds_clean_q(self, out=None, stream=None):
+        """The quadrature branch's rows of the current block (a RDS_QUAD pipeline, after rds() or rds_post()),
+        copied on `stream` into out [nch][>= n_rds] (a new tensor by default) without a synchronisation: what
+        RdsCarrier.feed takes beside rds_clean."""
+        import ctypes
+        import torch
+        p, s, n = C.c_void_p(), C.c_size_t(), C.c_int()
+        check(lib().sdr_ctx_rds_clean_q(self._h, C.byref(p), C.byref(s), C.byref(n)), "sdr_ctx_rds_clean_q")
+        if out is None:
+            out = torch.empty(self.nch, n.value, dtype=torch.float32, device=self.torch_device)
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != self.nch or out.shape[1] < n.value:
+            raise ValueError(f"out must be a float32 [{self.nch}][>= {n.value}] tensor")
+        rc = _hip().hipMemcpy2DAsync(ctypes.c_void_p(out.data_ptr()), ctypes.c_size_t(4 * _row_stride(out)), p,
+                                     ctypes.c_size_t(4 * s.value), ctypes.c_size_t(4 * n.value),
+                                     ctypes.c_size_t(self.nch), ctypes.c_int(3), ctypes.c_void_p(_stream(stream)))
+        if rc != 0:
+            raise SdrError(f"hipMemcpy2DAsync failed ({rc})")
         return out
 
     def buffer(self, name: str, stream=None):

@@ -107,6 +107,11 @@ int init_state(sdr_ctx* c, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(c->rband - HIST, 0, 2 * c->fm_par * sizeof(float), s));
     HIP_TRY(hipMemsetAsync(c->rdc - HIST, 0, 2 * c->fm_par * sizeof(float), s));
     HIP_TRY(hipMemsetAsync(c->rfilt - HIST, 0, 2 * c->rf_par * sizeof(float), s));
+    if (c->flags & SDR_FLAG_RDS_QUAD) {             // ipll_q[0] of the first block is 0.0f: a zeroed out buffer
+        HIP_TRY(hipMemsetAsync(c->rdc_q - HIST, 0, 2 * c->fm_par * sizeof(float), s));
+        HIP_TRY(hipMemsetAsync(c->rfilt_q - HIST, 0, 2 * c->rf_par * sizeof(float), s));
+        HIP_TRY(hipMemsetAsync(c->ipll_q_last, 0, (size_t)2 * c->nch * sizeof(float), s));
+    }
     const size_t tail_bytes = (size_t)2 * c->nch * 2 * (c->ntaps - 1);
     hipLaunchKernelGGL(k_fill_u8, dim3((unsigned)((tail_bytes + 255) / 256)), dim3(256), 0, s, c->tail,
                        (uint8_t)128, tail_bytes);  // u8 128 == 0.0f: zero FIR state
@@ -286,6 +291,8 @@ int sdr_ctx_create(sdr_ctx** out, int device, int nch, int mode, int rds_on, int
     *out = nullptr;
     if ((flags & SDR_FLAG_FAST_FRONTEND) && (flags & SDR_FLAG_PHASE_DEMOD))
         return fail(SDR_E_INVALID, "SDR_FLAG_PHASE_DEMOD needs the exact front end (not SDR_FLAG_FAST_FRONTEND)");
+    if ((flags & SDR_FLAG_RDS_QUAD) && !(rds_on && sdr_rds_mode_ok(mode)))
+        return fail(SDR_E_INVALID, "SDR_FLAG_RDS_QUAD needs rds_on and mode 0 (mode %d, rds_on %d)", mode, rds_on);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0)
         return fail(SDR_E_NODEV, "no HIP device %d", device);
@@ -420,6 +427,10 @@ int sdr_ctx_create(sdr_ctx** out, int device, int nch, int mode, int rds_on, int
     TRY(dalloc(c, &base, 2 * c->fm_par)); c->rband = base + HIST;
     TRY(dalloc(c, &base, 2 * c->fm_par)); c->rdc = base + HIST;
     TRY(dalloc(c, &base, 2 * c->rf_par)); c->rfilt = base + HIST;
+    if (flags & SDR_FLAG_RDS_QUAD) {
+        TRY(dalloc(c, &base, 2 * c->fm_par)); c->rdc_q = base + HIST;
+        TRY(dalloc(c, &base, 2 * c->rf_par)); c->rfilt_q = base + HIST;
+    }
     c->plain_stride = round_up((size_t)in.block_if, 64);
     c->pll_stride = round_up((size_t)in.block_if + 1, 64);
     c->clean_stride = round_up((size_t)in.n_rds, 64);
@@ -445,6 +456,10 @@ int sdr_ctx_create(sdr_ctx** out, int device, int nch, int mode, int rds_on, int
     TRY(dalloc(c, &c->carrier, 2 * c->pll_par));
     TRY(dalloc(c, &c->ipll, 2 * c->pll_par));
     TRY(dalloc(c, &c->rds_clean, c->clean_stride * nch));
+    if (flags & SDR_FLAG_RDS_QUAD) {
+        TRY(dalloc(c, &c->rds_clean_q, c->clean_stride * nch));
+        TRY(dalloc(c, &c->ipll_q_last, (size_t)2 * nch));
+    }
     TRY(dalloc(c, &c->tail, (size_t)2 * nch * 2 * (T - 1)));
     {
         std::vector<uint32_t> pad(64, 0x80808080u);
@@ -530,9 +545,14 @@ int sdr_ctx_buffer(sdr_ctx* c, const char* name, const float** ptr, size_t* stri
         {"rds_dc", c->rdc + p * c->fm_par, c->fm_stride, in.block_if},
         {"rds_filt", c->rfilt + p * c->rf_par, c->rf_stride, in.n_rds},
         {"rds_clean", c->rds_clean, c->clean_stride, in.n_rds},
+        // SDR_FLAG_RDS_QUAD only (null pointers without it: refused below)
+        {"rds_dc_q", c->rdc_q ? c->rdc_q + p * c->fm_par : nullptr, c->fm_stride, in.block_if},
+        {"rds_filt_q", c->rfilt_q ? c->rfilt_q + p * c->rf_par : nullptr, c->rf_stride, in.n_rds},
+        {"rds_clean_q", c->rds_clean_q, c->clean_stride, in.n_rds},
     };
     for (const E& e : tab) {
         if (std::strcmp(e.n, name) == 0) {
+            if (!e.p) return fail(SDR_E_INVALID, "buffer %s needs SDR_FLAG_RDS_QUAD", name);
             *ptr = e.p;
             *stride = e.s;
             *len = e.l;
@@ -540,6 +560,10 @@ int sdr_ctx_buffer(sdr_ctx* c, const char* name, const float** ptr, size_t* stri
         }
     }
     return fail(SDR_E_INVALID, "unknown buffer %s", name);
+}
+
+int sdr_ctx_rds_clean_q(sdr_ctx* c, const float** ptr, size_t* stride, int* len) {
+    return sdr_ctx_buffer(c, "rds_clean_q", ptr, stride, len);
 }
 
 }  // extern "C"

@@ -274,6 +274,9 @@ struct sdr_ctx {
     float *pilot_neg = nullptr, *gpilot_neg = nullptr;  // -pilot, -gen_pilot (the lane-pair PLL's input)
     float *pilot = nullptr, *band = nullptr, *gpilot = nullptr, *carrier = nullptr, *ipll = nullptr,
           *rds_clean = nullptr, *t_st = nullptr, *t_rds = nullptr;
+    // SDR_FLAG_RDS_QUAD (allocated only with it): the quadrature branch's extended streams, laid out as rdc and
+    // rfilt are, its output rows, and ipll_q[n] of the last block of each parity, [2][nch]
+    float *rdc_q = nullptr, *rfilt_q = nullptr, *rds_clean_q = nullptr, *ipll_q_last = nullptr;
     int* rds_ptq = nullptr;                             // RDS resampler (q << 8 | phase) per output
     bool rdsbb_all101 = false;                          // every RDS polyphase row has 101 taps
     bool audio_u1_101 = false;                          // audio resampler U == 1 with 101 taps

@@ -881,6 +881,68 @@ __global__ __launch_bounds__(BLK) void k_rds_mix(const RdsMix a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The quadrature branch's carrier and mixer (SDR_FLAG_RDS_QUAD; no reference counterpart, the definition is
+// at sdr_ctx_rds_clean_q in sdr_amd.h): k_rds_mix with phaseAdjust -pi/2 into streams of its own. It reads
+// what k_rds_mix reads (rband, the PLL's phases) and writes no PLL state: ipll_q[n], the next block's
+// ipll_q[0], goes to the row of this parity, and ipll_q[0] comes from the other parity's.
+// ------------------------------------------------------------------------------------------
+struct RdsMixQ {
+    const float* rband;         // this parity's rds_band, extended
+    const float* t;             // PLL phases of this parity
+    size_t fm_stride, plain_stride;
+    float* last;                // [nch] ipll_q[n] of this block
+    const float* last_prev;     // [nch] the previous block's
+    float ncoScale, phaseAdjust;
+    float* rdc;                 // this parity's rds_dc_q, extended (history copied by tile 0)
+    const float* rdc_prev;
+    float* rfilt;               // this parity's rds_filt_q, extended: its history is copied by tile 0 too
+    const float* rfilt_prev;
+    size_t rf_stride;
+    int n, n_rds;
+};
+
+__global__ __launch_bounds__(BLK) void k_rds_mix_q(const RdsMixQ a) {
+    const int ch = blockIdx.y;
+    const int i0 = ((int)blockIdx.x * BLK + (int)threadIdx.x) * MIX_R;
+    const float* tt = a.t + (size_t)ch * a.plain_stride;
+    const float* rb = a.rband + (size_t)ch * a.fm_stride;
+    float* y = a.rdc + (size_t)ch * a.fm_stride;
+    auto carrier = [&](int i, float tprev) {
+        return (i == 0) ? a.last_prev[ch] : nco_carrier(tprev, a.ncoScale, a.phaseAdjust);
+    };
+    if (i0 + MIX_R <= a.n) {
+        const float4 tv = *reinterpret_cast<const float4*>(tt + i0);
+        const float tm = i0 > 0 ? tt[i0 - 1] : 0.0f;
+        const float2 r01 = *reinterpret_cast<const float2*>(rb + i0 - 50);
+        const float2 r23 = *reinterpret_cast<const float2*>(rb + i0 - 48);
+        const float tp[MIX_R] = {tm, tv.x, tv.y, tv.z};
+        const float dl[MIX_R] = {r01.x, r01.y, r23.x, r23.y};
+        float o[MIX_R];
+#pragma unroll
+        for (int k = 0; k < MIX_R; k++) {
+            const float d = dl[k] + 0.0f;
+            o[k] = 2 * d * carrier(i0 + k, tp[k]);
+        }
+        *reinterpret_cast<float4*>(y + i0) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+        for (int k = 0; k < MIX_R; k++) {
+            const int i = i0 + k;
+            if (i < a.n) {
+                const float d = rb[i - 50] + 0.0f;
+                y[i] = 2 * d * carrier(i, i > 0 ? tt[i - 1] : 0.0f);
+            } else if (i == a.n) {
+                a.last[ch] = nco_carrier(tt[a.n - 1], a.ncoScale, a.phaseAdjust);
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < HIST) {
+        y[(int)threadIdx.x - HIST] = a.rdc_prev[(size_t)ch * a.fm_stride + a.n - HIST + threadIdx.x];
+        a.rfilt[(size_t)ch * a.rf_stride + (int)threadIdx.x - HIST] =
+            a.rfilt_prev[(size_t)ch * a.rf_stride + a.n_rds - HIST + threadIdx.x];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Mixers. stereo.cpp:83-85: stereo_dc = 2.0*band*carrier (f64 product, one rounding).
 // rds.cpp:125-127: rds_dc = (2*delay)*ipll with delay[i] = rds_band[i-50] (the 101-tap APF of
 // filter.cpp:73-78 is an exact 50-sample delay for finite inputs). Also copies the history.
@@ -1605,6 +1667,32 @@ int sdr_frontend_pre_parts(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, int 
     return sdr_plls_signal(c, stream);   // the whole block: the launch's flag
 }
 
+// SDR_FLAG_RDS_QUAD: the quadrature carrier and mixer of the current block (nothing without the flag). Both
+// paths of sdr_rds_post launch it before they record REL_RDS: it reads rband and t_rds of this parity.
+static int rds_mix_q_launch(sdr_ctx* c, hipStream_t s) {
+    if (!(c->flags & SDR_FLAG_RDS_QUAD)) return SDR_OK;
+    const int n = c->info.block_if, p = c->parity;
+    RdsMixQ a{};
+    a.rband = c->rband + p * c->fm_par;
+    a.t = c->plain(c->t_rds);
+    a.fm_stride = c->fm_stride;
+    a.plain_stride = c->plain_stride;
+    a.last = c->ipll_q_last + (size_t)p * c->nch;
+    a.last_prev = c->ipll_q_last + (size_t)(p ^ 1) * c->nch;
+    a.ncoScale = 0.5f;
+    a.phaseAdjust = -(float)(M_PI / 2);
+    a.rdc = c->rdc_q + p * c->fm_par;
+    a.rdc_prev = c->rdc_q + (p ^ 1) * c->fm_par;
+    a.rfilt = c->rfilt_q + p * c->rf_par;
+    a.rfilt_prev = c->rfilt_q + (p ^ 1) * c->rf_par;
+    a.rf_stride = c->rf_stride;
+    a.n = n;
+    a.n_rds = c->info.n_rds;
+    hipLaunchKernelGGL(k_rds_mix_q, dim3(cdiv(n + 1, BLK * MIX_R), c->nch), dim3(BLK), 0, s, a);
+    LAUNCH_CHECK();
+    return SDR_OK;
+}
+
 int sdr_rds_post(sdr_ctx* c, float* rds_clean, size_t rds_stride, void* stream) {
     if (!c) return fail(SDR_E_INVALID, "null context");
     if (const int rf_ = check_failed(c, "rds_post")) return rf_;
@@ -1639,6 +1727,7 @@ int sdr_rds_post(sdr_ctx* c, float* rds_clean, size_t rds_stride, void* stream) 
         a.n_rds = in.n_rds;
         hipLaunchKernelGGL(k_rds_mix, dim3(cdiv(n + 1, BLK * MIX_R), c->nch), dim3(BLK), 0, s, a);
         LAUNCH_CHECK();
+        if (const int rq = rds_mix_q_launch(c, s)) return rq;          // (before the release: it reads rband, t_rds)
         if (const int rr = release_record(c, REL_RDS, s)) return rr;   // rband, t_rds, ipll read
     } else {
         {
@@ -1651,6 +1740,7 @@ int sdr_rds_post(sdr_ctx* c, float* rds_clean, size_t rds_stride, void* stream) 
         hipLaunchKernelGGL(k_mix<true>, dim3(cdiv(n, BLK), c->nch), dim3(BLK), 0, s, rband, c->fm_stride,
                            c->pllbuf(c->ipll), c->pll_stride, n, rdc, c->rdc + (p ^ 1) * c->fm_par, c->fm_stride, 50);
         LAUNCH_CHECK();
+        if (const int rq = rds_mix_q_launch(c, s)) return rq;
         if (const int rr = release_record(c, REL_RDS, s)) return rr;
         hipLaunchKernelGGL(k_hist_copy, dim3(c->nch), dim3(HIST), 0, s, rfilt, c->rfilt + (p ^ 1) * c->rf_par,
                            c->rf_stride, in.n_rds);
@@ -1676,6 +1766,20 @@ int sdr_rds_post(sdr_ctx* c, float* rds_clean, size_t rds_stride, void* stream) 
         f.ydup_stride = rds_stride;
         f.err = block_poison(c);                    // NaN rows after a persistent PLL or release timeout
         const int r = fir_rb<1, false>(c, rfilt, c->rf_stride, in.n_rds, f, s);
+        if (r) return r;
+    }
+    if (c->flags & SDR_FLAG_RDS_QUAD) {                 // the same resampler and RRC over the quadrature mixer's stream
+        float* rfilt_q = c->rfilt_q + p * c->rf_par;
+        hipLaunchKernelGGL(kr, gr, dim3(RLC_BLK), resample_lc_lds_bytes(c->rdsbb_L, 247, 640, !c->rdsbb_all101), s,
+                           c->rdc_q + p * c->fm_par, c->fm_stride, -HIST, c->rdsbb_pp, c->rdsbb_cnt, c->rdsbb_L, c->rds_ptq,
+                           in.n_rds, c->nch, rfilt_q, c->rf_stride);
+        LAUNCH_CHECK();
+        FirRb f{};
+        f.h[0] = c->rrc_h;
+        f.y[0] = c->rds_clean_q;
+        f.y_stride[0] = c->clean_stride;
+        f.err = block_poison(c);
+        const int r = fir_rb<1, false>(c, rfilt_q, c->rf_stride, in.n_rds, f, s);
         if (r) return r;
     }
     c->rds_dsp_done = c->block;

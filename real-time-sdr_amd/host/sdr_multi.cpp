@@ -2,7 +2,7 @@
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
 //   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
-//             [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L]]
+//             [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L] [--rds-carrier ref|quad]]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //   sdr_multi NCH --wide W [--shift S] --tune FILE ...          (the receiver on wide captures)
 //   sdr_multi NWIDE --wide W [--shift S] --scan ...             (the scan of wide captures)
@@ -49,6 +49,11 @@
 // the decoder first searches a failing block over the flips of its L least reliable raw decisions
 // (sdr_rds_groups_soft); in PREFIX.groups a block placed that way ends in "~", PREFIX.radio gains a "soft:" line
 // per channel, and every other file stays that of a run without it.
+// --rds-carrier quad (with --rds-clock track): coherent RDS -- the RDS chain also runs with the quadrature of its
+// carrier (SDR_FLAG_RDS_QUAD), the carrier-phase derotator (sdr_rds_carrier_*) turns both branches' rows onto one
+// axis and the tracker reads those rows instead of rds_clean (ref, the default); PREFIX.groups and PREFIX.radio
+// are made from the new bits, PREFIX.radio gains a "carrier:" line per channel, and every other file stays that
+// of a run without it.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -68,7 +73,7 @@
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
-                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L]]\n"
+                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L] [--rds-carrier ref|quad]]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
                          "       sdr_multi NCH --wide W [--shift S] --tune FILE ...   |   sdr_multi NWIDE --wide W [--shift S] --scan ...\n"
@@ -84,6 +89,8 @@ namespace {
                          "            the whole bit) instead of the per-block clock recovery (ref, default); needs --rds-decode, mode 0\n"
                          "  --rds-soft L: soft decisions, a failing block is searched over the flips of its L (1-6) least reliable\n"
                          "            bits before the burst table; needs --rds-clock track\n"
+                         "  --rds-carrier quad: coherent RDS, the chain's quadrature branch too and both turned onto one axis by the\n"
+                         "            carrier phase found in them, for the tracker (ref, default: rds_clean alone); needs --rds-clock track\n"
                          "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n"
                          "  --wide W: the input is wide int8 I/Q at W (4, 8, 10) times rf_Fs, rows of 2*W*block_iq bytes, each\n"
                          "            split into 2W-1 capture rows (--shift S: output shift 1-24); needs --tune or --scan\n");
@@ -100,6 +107,7 @@ int main(int argc, char** argv) {
     if (o.nch <= 0) usage();
     bool scan = false, meter = false, blend = false, finish = false, rds_decode = false, rds_correct = false, rds_clock_set = false;
     int rds_clock = SDR_MULTI_RDS_CLOCK_REF, rds_soft = 0;
+    bool rds_quad = false;
     sdr_rds_opts ro{};
     sdr_rds_opts_default(&ro);
     int wide_w = 0, wide_shift = 0;
@@ -153,6 +161,12 @@ int main(int argc, char** argv) {
             if (n.size() != 1 || n[0] < '1' || n[0] > '6') usage();
             rds_soft = n[0] - '0';
         }
+        else if (a == "--rds-carrier" && i + 1 < argc) {
+            const std::string c = argv[++i];
+            if (c == "quad") rds_quad = true;
+            else if (c == "ref") rds_quad = false;
+            else usage();
+        }
         else if (a == "--fast") o.flags |= SDR_FLAG_FAST_FRONTEND;
         else if (a == "--demod" && i + 1 < argc) {
             const std::string d = argv[++i];
@@ -169,6 +183,7 @@ int main(int argc, char** argv) {
     if (blend && !meter) usage();
     if ((rds_correct || rds_clock_set) && !rds_decode) usage();
     if (rds_soft && (!rds_decode || rds_clock != SDR_MULTI_RDS_CLOCK_TRACK)) usage();   // only the tracker has reliabilities
+    if (rds_quad && (!rds_decode || rds_clock != SDR_MULTI_RDS_CLOCK_TRACK)) usage();   // the tracker reads the rotated rows
     if (rds_decode && (scan || !sdr_rds_mode_ok(o.mode))) usage();   // a scan demodulates nothing; modes 1-3 have no RDS bit clock
     if (wide_shift && !wide_w) usage();
     if (wide_w && !scan && tune_path.empty()) usage();        // a wide run is always tuned
@@ -254,8 +269,11 @@ int main(int argc, char** argv) {
     const sdr_multi_tuning* tp = tune_path.empty() ? nullptr : &tune;
     const sdr_multi_rds rd{ro.max_burst, ro.loss_blocks};
     const sdr_rds_soft_opts sq{ro.max_burst, ro.loss_blocks, rds_soft};
-    const int rc = rds_decode ? sdr_multi_run_rds_soft(&o, wide_w ? &wd : nullptr, tp, meter ? &mo : nullptr, finish ? &ao : nullptr,
-                                                       blend ? 1 : 0, &rd, rds_clock, nullptr, rds_soft ? &sq : nullptr, &st)
+    sdr_rds_carrier_opts cq{};
+    sdr_rds_carrier_opts_default(&cq);
+    const int rc = rds_decode ? sdr_multi_run_rds_carrier(&o, wide_w ? &wd : nullptr, tp, meter ? &mo : nullptr,
+                                                          finish ? &ao : nullptr, blend ? 1 : 0, &rd, rds_clock, nullptr,
+                                                          rds_soft ? &sq : nullptr, rds_quad ? &cq : nullptr, &st)
                    : wide_w ? sdr_multi_run_wide(&o, &wd, tp, meter ? &mo : nullptr, finish ? &ao : nullptr, blend ? 1 : 0, &st)
                    : finish ? sdr_multi_run_finished(&o, tp, meter ? &mo : nullptr, &ao, blend ? 1 : 0, &st)
                    : meter ? sdr_multi_run_metered(&o, tp, &mo, &st)

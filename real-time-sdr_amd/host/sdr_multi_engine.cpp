@@ -57,6 +57,7 @@
 #include <algorithm>
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
@@ -104,6 +105,7 @@ struct RunSpec {
     int rds_clock = SDR_MULTI_RDS_CLOCK_REF;  //   whose bits it reads (sdr_multi_run_rds_clock)
     const sdr_rds_track_opts* track = nullptr;   // the tracker's options, with SDR_MULTI_RDS_CLOCK_TRACK
     const sdr_rds_soft_opts* soft = nullptr;  // soft decisions on the tracker's clock (sdr_multi_run_rds_soft)
+    const sdr_rds_carrier_opts* carrier = nullptr;   // the derotated rows for the tracker (sdr_multi_run_rds_carrier)
 };
 
 // Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused.
@@ -111,6 +113,7 @@ bool validate(const RunSpec& r) {
     const sdr_multi_opts* o = r.o;
     if (!o || (r.blend && (!r.meter || !r.audio))) return false;
     if ((o->flags & SDR_FLAG_FAST_FRONTEND) && (o->flags & SDR_FLAG_PHASE_DEMOD)) return false;   // sdr_ctx_create's rule
+    if (o->flags & SDR_FLAG_RDS_QUAD) return false;   // the engine sets it itself, on the RDS thread's context (carrier)
     if (r.audio) {   // what sdr_audio_create would refuse
         float a = 0.0f, b = 0.0f;
         if (sdr_audio_coeffs(o->mode, r.audio->tau_us, &a, &b) != SDR_OK || !(r.audio->blend_hi > r.audio->blend_lo)) return false;
@@ -130,6 +133,10 @@ bool validate(const RunSpec& r) {
         if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds) return false;
         if (q->max_burst < 0 || q->max_burst > 5 || q->loss_blocks < 1 || q->loss_blocks > 64 || q->soft_bits < 0 || q->soft_bits > 6)
             return false;
+    }
+    if (const sdr_rds_carrier_opts* q = r.carrier) {   // the tracker reads its rows; what sdr_rds_carrier_create would refuse
+        if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds) return false;
+        if (q->qshift < 0 || q->qshift > 15 || q->avg_shift < 0 || q->avg_shift > 6) return false;
     }
     if (const sdr_multi_tuning* t = r.tune) {   // the tuning's bounds (sdr_tuner_set's)
         int N = 0;
@@ -422,8 +429,12 @@ struct RdsRes {
     DevBuf<uint8_t> d_tbits;
     // ... with soft decisions (sdr_multi_run_rds_soft): the tracker's reliabilities of those bits
     DevBuf<uint16_t> d_tsoft;
+    // ... on the derotated rows (sdr_multi_run_rds_carrier): the derotator and the rows it writes for the tracker
+    sdr_rds_carrier* car = nullptr;
+    DevBuf<float> d_rot;
+    size_t rot_stride = 0;
     RdsRes(const sdr_multi_opts& o, const sdr_multi_rds* rds, const sdr_rds_track_opts* track, const sdr_rds_soft_opts* soft,
-           bool cache) {
+           const sdr_rds_carrier_opts* carrier, int n_rds, bool cache) {
         const int nch = o.nch;
         pre.make();
         pll.make();
@@ -447,8 +458,13 @@ struct RdsRes {
         d_tnbits.get((size_t)nch);
         d_tbits.get((size_t)nch * SDR_MAX_BITS);
         if (soft) d_tsoft.get((size_t)nch * SDR_MAX_BITS);
+        if (!carrier) return;
+        check_sdr(sdr_rds_carrier_create(&car, o.device, nch, o.mode, carrier), "sdr_rds_carrier_create");
+        rot_stride = ((size_t)n_rds + 3) & ~(size_t)3;   // every row on a 16-byte boundary
+        d_rot.get((size_t)nch * rot_stride);
     }
     ~RdsRes() {
+        if (car) (void)sdr_rds_carrier_destroy(car);
         if (trk) (void)sdr_rds_track_destroy(trk);
         if (dec) (void)sdr_rds_dec_destroy(dec);
     }
@@ -936,6 +952,16 @@ void rds_thread(Shared* sh) {
             size_t clean_stride = 0;
             int n_rds = 0;
             check_sdr(sdr_ctx_buffer(ctx, "rds_clean", &clean, &clean_stride, &n_rds), "sdr_ctx_buffer");
+            if (r.car) {   // both branches' rows onto one axis first: the tracker reads the rotated rows
+                const float* clean_q = nullptr;
+                size_t q_stride = 0;
+                int n_q = 0;
+                check_sdr(sdr_ctx_rds_clean_q(ctx, &clean_q, &q_stride, &n_q), "sdr_ctx_rds_clean_q");
+                check_sdr(sdr_rds_carrier_rotate(r.car, clean, clean_stride, clean_q, q_stride, n_rds, r.d_rot.p, r.rot_stride, s),
+                          "sdr_rds_carrier_rotate");
+                clean = r.d_rot.p;
+                clean_stride = r.rot_stride;
+            }
             if (r.d_tsoft.p)
                 check_sdr(sdr_rds_track_bits_soft(r.trk, clean, clean_stride, n_rds, r.d_tnbits.p, r.d_tbits.p, SDR_MAX_BITS,
                                                   r.d_tsoft.p, SDR_MAX_BITS, s),
@@ -1014,6 +1040,8 @@ void rds_thread(Shared* sh) {
         if (r.trk) check_sdr(sdr_rds_track_stats_read(r.trk, clock.data(), sh->s_post_c[1]), "sdr_rds_track_stats_read");
         std::vector<sdr_rds_soft_stats> soft(r.d_tsoft.p ? (size_t)o.nch : 0);
         if (r.d_tsoft.p) check_sdr(sdr_rds_soft_stats_read(r.dec, soft.data(), sh->s_post_c[1]), "sdr_rds_soft_stats_read");
+        std::vector<sdr_rds_carrier_stats> carrier(r.car ? (size_t)o.nch : 0);
+        if (r.car) check_sdr(sdr_rds_carrier_stats_read(r.car, carrier.data(), sh->s_post_c[1]), "sdr_rds_carrier_stats_read");
         File radio;
         radio.open(std::string(o.out_prefix) + ".radio", "w");
         std::vector<char> buf(4096);
@@ -1026,6 +1054,12 @@ void rds_thread(Shared* sh) {
             const sdr_rds_track_stats& k = clock[(size_t)c];
             std::fprintf(radio, "ch %d: clock: locked %u phase %u bits %u moves %u half_moves %u resets %u level %u\n", c, k.locked,
                          k.phase, k.bits, k.moves, k.half_moves, k.resets, k.level);
+            if (r.car) {   // the phase in degrees, and hypot(sr, si) / st: 1 for a clean subcarrier, near 0 for noise
+                const sdr_rds_carrier_stats& q = carrier[(size_t)c];
+                const double coherence = q.st > 0 ? std::hypot((double)q.sr, (double)q.si) / (double)q.st : 0.0;
+                std::fprintf(radio, "ch %d: carrier: phase %.2f coherence %.3f windows %u resets %u\n", c,
+                             (double)q.phi * (360.0 / 4294967296.0), coherence, q.windows, q.resets);
+            }
             if (r.d_tsoft.p)
                 std::fprintf(radio, "ch %d: soft: blocks %u flips %u\n", c, soft[(size_t)c].soft_blocks, soft[(size_t)c].soft_flips);
         }
@@ -1073,7 +1107,9 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     sh.tuned = spec.tune != nullptr;
     sh.rows = spec.wide ? spec.wide->nwide : spec.tune ? spec.tune->nsrc : spec.o->nch;
     const sdr_multi_opts& o = sh.o;
-    for (int i = 0; i < 3; i++) sh.ctx[i].take(o.device, o.nch, o.mode, i == 2, o.flags, sw.ctx_cache);
+    // (the RDS thread's context alone runs the quadrature branch, and only in a run that derotates)
+    for (int i = 0; i < 3; i++)
+        sh.ctx[i].take(o.device, o.nch, o.mode, i == 2, o.flags | (i == 2 && spec.carrier ? SDR_FLAG_RDS_QUAD : 0), sw.ctx_cache);
     mark("contexts");
     // pooled contexts keep their tuning over sdr_ctx_reset: set it on every context of a tuned run,
     // clear it on those of an untuned one
@@ -1118,7 +1154,8 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     mark("streams");
     const size_t lr_bytes = 2 * (size_t)sh.info.n_audio * o.nch * sizeof(int16_t);
     sh.ar.emplace(lr_bytes, sw.pin_cache);
-    sh.rr.emplace(o, spec.rds, spec.rds_clock == SDR_MULTI_RDS_CLOCK_TRACK ? spec.track : nullptr, spec.soft, sw.pin_cache);
+    sh.rr.emplace(o, spec.rds, spec.rds_clock == SDR_MULTI_RDS_CLOCK_TRACK ? spec.track : nullptr, spec.soft, spec.carrier,
+                  sh.info.n_rds, sw.pin_cache);
     if (spec.meter) sh.meter.emplace(o, *spec.meter, sw.pin_cache);
     if (spec.audio) sh.fin.emplace(o, *spec.audio, spec.blend, lr_bytes, sw.pin_cache);
     mark("consumer buffers");
@@ -1231,12 +1268,19 @@ extern "C" int sdr_multi_run_rds_soft(const sdr_multi_opts* opts, const sdr_mult
                                       const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, const sdr_multi_rds* rds,
                                       int rds_clock, const sdr_rds_track_opts* track, const sdr_rds_soft_opts* soft,
                                       sdr_multi_stats* stats) {
+    return sdr_multi_run_rds_carrier(opts, wide, tune, mo, ao, blend, rds, rds_clock, track, soft, nullptr, stats);
+}
+
+extern "C" int sdr_multi_run_rds_carrier(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
+                                         const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, const sdr_multi_rds* rds,
+                                         int rds_clock, const sdr_rds_track_opts* track, const sdr_rds_soft_opts* soft,
+                                         const sdr_rds_carrier_opts* carrier, sdr_multi_stats* stats) {
     if (rds_clock == SDR_MULTI_RDS_CLOCK_REF) {
-        if (soft) return SDR_E_INVALID;   // the reference clock has no reliabilities
+        if (soft || carrier) return SDR_E_INVALID;   // the reference clock has no reliabilities and reads rds_clean itself
         return sdr_multi_run_rds(opts, wide, tune, mo, ao, blend, rds, stats);
     }
     if (!rds || (wide && !tune)) return SDR_E_INVALID;
     sdr_rds_track_opts defaults;
     sdr_rds_track_opts_default(&defaults);
-    return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, rds_clock, track ? track : &defaults, soft}, stats);
+    return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, rds_clock, track ? track : &defaults, soft, carrier}, stats);
 }
