@@ -19,7 +19,7 @@ SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_ctx.hip $(PKG)/csrc/sdr_
             $(PKG)/csrc/sdr_taps.cpp $(PKG)/csrc/sdr_rds_text.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
 HDRS     := include/sdr_amd.h $(PKG)/csrc/pll_math.h $(PKG)/csrc/sdr_internal.h $(PKG)/csrc/demod_phase.h \
-            $(PKG)/csrc/nco.h $(PKG)/csrc/stage_device.h
+            $(PKG)/csrc/nco.h $(PKG)/csrc/stage_device.h $(PKG)/csrc/stage_host.h
 
 # host C++ (no device code): compiled by the system g++ against the HIP runtime headers
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include \

@@ -215,6 +215,8 @@ int sdr_tuner_table(int mode, float *cs, int max_pairs, int *n);
  * sdr_plls_signal. */
 int sdr_tuner_set(sdr_ctx *ctx, int nsrc, const int32_t *src, const int32_t *khz, void *stream);
 int sdr_tuner_get(const sdr_ctx *ctx, int *nsrc);          /* 0: not tuned */
+/* host only, no GPU: SDR_OK when sdr_tuner_set takes this tuning on a context of nch channels in `mode` */
+int sdr_tuner_check(int mode, int nch, int nsrc, const int32_t *src, const int32_t *khz);
 /* RF_frontend loop body for a tuned context: iq [nsrc][2*block_iq]. Same parity-release wait, timing
  * hooks (sdr_frontend_timing armed after sdr_tuner_set) and block advance as sdr_frontend. */
 int sdr_frontend_tuned(sdr_ctx *ctx, const uint8_t *iq, size_t iq_stride, void *stream);
@@ -305,6 +307,8 @@ int sdr_split_taps(int W, int16_t *g, int max_pairs, int *n);
  * aligned, or a rows / row_stride that sdr_frontend_tuned would refuse (row_stride >= 2 block_iq, both
  * even; 4-byte aligned rows are stored in whole dwords). */
 int sdr_split_create(sdr_split **out, int device, int mode, int W, int nwide, int shift);
+/* host only, no GPU: SDR_OK when sdr_split_create takes these arguments */
+int sdr_split_check(int mode, int W, int nwide, int shift);
 int sdr_split_destroy(sdr_split *s);
 int sdr_split_reset(sdr_split *s, void *stream);     /* history and clip counters back to 0 */
 /* one block of every stream: one launch on `stream`, no sync */
@@ -430,6 +434,8 @@ typedef struct sdr_audio_opts {
 void sdr_audio_opts_default(sdr_audio_opts *o);   /* 75, 0.5, 2.0 */
 /* host only, no GPU: the one-pole's coefficients of a mode */
 int sdr_audio_coeffs(int mode, float tau_us, float *a, float *b);
+/* host only, no GPU: SDR_OK when sdr_audio_create takes the record in `mode` (tau_us, blend_hi > blend_lo) */
+int sdr_audio_opts_check(int mode, const sdr_audio_opts *opts);
 typedef struct sdr_audio_state {   /* 24 bytes */
     float y[2], blend, gain, blend_target, gain_target;
 } sdr_audio_state;
@@ -510,6 +516,8 @@ int sdr_rds_correction_table(int max_burst, uint32_t *tab1024, int *entries);
 /* 1 when the mode's RDS chain recovers bits at 1187.5 bit/s -- its baseband rate if_Fs 247 / 640 is
  * 2375 symbol_Fs samples a second: mode 0 -- and 0 otherwise (modes 1 to 3, whose bits carry no groups) */
 int sdr_rds_mode_ok(int mode);
+/* host only, no GPU: SDR_OK when sdr_rds_dec_create takes the record, else SDR_E_INVALID and sdr_last_error */
+int sdr_rds_opts_check(const sdr_rds_opts *opts);
 /* device: the decoder is its own handle, like the meter. sdr_rds_groups enqueues one kernel (one wave per
  * channel) on `stream`; nbits_dev [nch] int32 and bits_dev [nch][bits_stride] are device arrays of
  * sdr_rds_bits' layout, ordered before it by the caller (the same stream does). Each call overwrites the
@@ -617,6 +625,8 @@ typedef struct sdr_rds_track_opts {
     int half_bits;                /* a multiple of SDR_RDS_TRACK_T in T..64 */
 } sdr_rds_track_opts;
 void sdr_rds_track_opts_default(sdr_rds_track_opts *o);   /* 10, 32, 64 */
+/* host only, no GPU: SDR_OK when sdr_rds_track_create takes the record in `mode` */
+int sdr_rds_track_opts_check(int mode, const sdr_rds_track_opts *opts);
 typedef struct sdr_rds_track sdr_rds_track;
 int sdr_rds_track_create(sdr_rds_track **out, int device, int nch, int mode, const sdr_rds_track_opts *opts);
 int sdr_rds_track_destroy(sdr_rds_track *t);
@@ -662,6 +672,8 @@ typedef struct sdr_rds_soft_opts {
     int soft_bits;               /* 0..6 */
 } sdr_rds_soft_opts;
 void sdr_rds_soft_opts_default(sdr_rds_soft_opts *o);   /* 2, 8, 6 */
+/* host only, no GPU: SDR_OK when sdr_rds_dec_create_soft takes the record */
+int sdr_rds_soft_opts_check(const sdr_rds_soft_opts *opts);
 typedef struct sdr_rds_soft_stats {   /* 16 bytes */
     uint32_t soft_blocks;        /* blocks placed by the soft step (they count in sdr_rds_stats.corrected too) */
     uint32_t soft_flips;         /* raw decisions flipped in them */
@@ -731,6 +743,8 @@ typedef struct sdr_rds_carrier_opts {
     int avg_shift;                /* 0..6: S += (P - S) >> avg_shift */
 } sdr_rds_carrier_opts;
 void sdr_rds_carrier_opts_default(sdr_rds_carrier_opts *o);   /* 10, 3 */
+/* host only, no GPU: SDR_OK when sdr_rds_carrier_create takes the record in `mode` */
+int sdr_rds_carrier_opts_check(int mode, const sdr_rds_carrier_opts *opts);
 typedef struct sdr_rds_carrier sdr_rds_carrier;
 int sdr_rds_carrier_create(sdr_rds_carrier **out, int device, int nch, int mode, const sdr_rds_carrier_opts *opts);
 int sdr_rds_carrier_destroy(sdr_rds_carrier *h);

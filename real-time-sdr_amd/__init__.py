@@ -333,6 +333,50 @@ def _stream(stream=None) -> int | None:
     return int(torch.cuda.current_stream().cuda_stream) or None
 
 
+def _opts(struct, default_fn_name: str, label: str, **opts):
+    """An options record: the library's defaults (default_fn_name) with the given fields replaced."""
+    o = struct()
+    getattr(lib(), default_fn_name)(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(struct._fields_):
+            raise SdrError(f"{label}: unknown option {k}", -1)
+        setattr(o, k, v)
+    return o
+
+
+def _dtype(struct):
+    """numpy dtype of a record of the C ABI."""
+    import numpy as np
+    return np.dtype(struct)
+
+
+class _Handle:
+    """What the stage handles share: ._h (made by the subclass) is destroyed once, by close() or at the
+    object's end; reset(); and the read of one record per channel. _destroy and _reset name the library's calls."""
+    _destroy = _reset = ""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(getattr(lib(), self._reset)(self._h, _stream(stream)), self._reset)
+
+    def _records(self, fn_name: str, dtype, stream=None):
+        """numpy structured array [nch] filled by fn_name(handle, host, stream); synchronises the stream."""
+        import numpy as np
+        out = np.zeros(self.nch, dtype)
+        check(getattr(lib(), fn_name)(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), fn_name)
+        return out
+
+
 def _row_stride(t) -> int:
     """Elements between consecutive channels of a 2-D [nch][len] tensor (last dim contiguous)."""
     assert t.dim() == 2 and t.stride(1) == 1, "expected a [nch][len] tensor with a contiguous last dim"
@@ -403,13 +447,7 @@ def scan_window(mode: int):
 
 def scan_opts(**opts) -> ScanOpts:
     """The picker's defaults (sdr_scan_opts_default) with the given fields replaced."""
-    o = ScanOpts()
-    lib().sdr_scan_opts_default(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(ScanOpts._fields_):
-            raise SdrError(f"scan_pick: unknown option {k}", -1)
-        setattr(o, k, v)
-    return o
+    return _opts(ScanOpts, "sdr_scan_opts_default", "scan_pick", **opts)
 
 
 def scan_pick(mode: int, psd_row, max=None, **opts):
@@ -431,9 +469,11 @@ def scan_pick(mode: int, psd_row, max=None, **opts):
     return khz[:k], db[:k]
 
 
-class Scanner:
+class Scanner(_Handle):
     """The band scan of `nsrc` capture rows of one mode (sdr_scan_*): block(iq) per block of the rows
     sdr_frontend_tuned reads, then psd() or stations(). Its own handle: no channels, any stream."""
+
+    _destroy, _reset = "sdr_scan_destroy", "sdr_scan_reset"
 
     def __init__(self, mode: int, nsrc: int, device: int = 0):
         h = C.c_void_p()
@@ -441,20 +481,6 @@ class Scanner:
         self._h = h
         self.mode, self.nsrc, self.device = mode, nsrc, device
         self.n_bins, self.segments_per_block, self.block_iq = scan_geometry(mode)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_scan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_scan_reset(self._h, _stream(stream)), "sdr_scan_reset")
 
     def block(self, iq, stream=None):
         """iq: uint8 [nsrc][2*block_iq] (device); enqueues, no sync."""
@@ -504,9 +530,11 @@ def split_taps(W: int):
     return g
 
 
-class Splitter:
+class Splitter(_Handle):
     """`nwide` wide int8 I/Q captures at W * rf_Fs into nwide * (2 W - 1) capture rows at rf_Fs, the rows
     sdr_frontend_tuned and the Scanner read (sdr_split_*). Its own handle: no channels, any stream."""
+
+    _destroy, _reset = "sdr_split_destroy", "sdr_split_reset"
 
     def __init__(self, W: int, nwide: int, mode: int = 0, device: int = 0, shift=None):
         h = C.c_void_p()
@@ -517,20 +545,6 @@ class Splitter:
         self.rows, self.taps, self.wide_iq, self.half_khz, d = split_geometry(mode, W)
         self.shift = d if shift is None or shift <= 0 else int(shift)
         self.block_iq = self.wide_iq // W
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_split_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_split_reset(self._h, _stream(stream)), "sdr_split_reset")
 
     def block(self, wide, out=None, stream=None):
         """wide: int8 [nwide][2*W*block_iq] (device). Returns the uint8 rows [nwide*R][2*block_iq] (out, or
@@ -558,8 +572,7 @@ class Splitter:
 # ------------------------------------------------------------------ reception meter (include/sdr_amd.h, sdr_meter_*)
 def meter_row_dtype():
     """numpy dtype of sdr_meter_row (64 bytes)."""
-    import numpy as np
-    return np.dtype(MeterRow)
+    return _dtype(MeterRow)
 
 
 def meter_taps(mode: int):
@@ -574,13 +587,7 @@ def meter_taps(mode: int):
 
 def meter_opts(**opts) -> MeterOpts:
     """The status thresholds' defaults (sdr_meter_opts_default) with the given fields replaced."""
-    o = MeterOpts()
-    lib().sdr_meter_opts_default(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(MeterOpts._fields_):
-            raise SdrError(f"meter_status: unknown option {k}", -1)
-        setattr(o, k, v)
-    return o
+    return _opts(MeterOpts, "sdr_meter_opts_default", "meter_status", **opts)
 
 
 def meter_status(mode: int, rows, **opts):
@@ -621,30 +628,18 @@ def meter_deviation(mode: int, rows):
     return out.reshape(rows.shape)
 
 
-class Meter:
+class Meter(_Handle):
     """The reception meter of `nch` channels of one mode (sdr_meter_*): per block audio(pipe, lr) after
     the block's stereo stage and rds(pipe) after its RDS stage -- on one Pipeline or on two joined by
     push_fm_demod -- then rows() or status(). Its own handle; the rows stay on the device."""
+
+    _destroy, _reset = "sdr_meter_destroy", "sdr_meter_reset"
 
     def __init__(self, nch: int, mode: int = 0, device: int = 0):
         h = C.c_void_p()
         check(lib().sdr_meter_create(C.byref(h), device, nch, mode), "sdr_meter_create")
         self._h = h
         self.nch, self.mode, self.device = nch, mode, device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_meter_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_meter_reset(self._h, _stream(stream)), "sdr_meter_reset")
 
     def audio(self, pipe: "Pipeline", lr=None, stream=None):
         """The fm, pilot, noise and audio fields of pipe's current block; lr: the int16 [nch][2*n_audio]
@@ -658,10 +653,7 @@ class Meter:
 
     def rows(self, stream=None):
         """numpy structured array [nch] of meter_row_dtype(); synchronises the stream."""
-        import numpy as np
-        out = np.zeros(self.nch, meter_row_dtype())
-        check(lib().sdr_meter_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_meter_read")
-        return out
+        return self._records("sdr_meter_read", meter_row_dtype(), stream)
 
     def rows_into(self, out, stream=None):
         """The rows copied on the device into `out` (a contiguous uint8 tensor of nch * 64 bytes) in
@@ -698,26 +690,21 @@ def audio_coeffs(mode: int, tau_us: float):
 
 def audio_opts(**opts) -> AudioOpts:
     """The finishing stage's defaults (sdr_audio_opts_default) with the given fields replaced."""
-    o = AudioOpts()
-    lib().sdr_audio_opts_default(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(AudioOpts._fields_):
-            raise SdrError(f"audio_opts: unknown option {k}", -1)
-        setattr(o, k, v)
-    return o
+    return _opts(AudioOpts, "sdr_audio_opts_default", "audio_opts", **opts)
 
 
 def audio_state_dtype():
     """numpy dtype of sdr_audio_state (24 bytes)."""
-    import numpy as np
-    return np.dtype(AudioState)
+    return _dtype(AudioState)
 
 
-class AudioFinish:
+class AudioFinish(_Handle):
     """The finishing stage of `nch` channels of one mode (sdr_audio_*): de-emphasis, stereo blend and
     gain over the int16 rows stereo() (width 2) or mono() (width 1) wrote. Per block, optionally
     set_control(blend, gain) or blend_from_meter(meter) after meter.audio, then finish(lr). Its own handle;
     the state stays on the device. opts: tau_us (75; 50 outside the Americas; 0 off), blend_lo, blend_hi."""
+
+    _destroy, _reset = "sdr_audio_destroy", "sdr_audio_reset"
 
     def __init__(self, nch: int, mode: int = 0, width: int = 2, device: int = 0, **opts):
         h = C.c_void_p()
@@ -725,20 +712,6 @@ class AudioFinish:
         check(lib().sdr_audio_create(C.byref(h), device, nch, mode, width, C.byref(o)), "sdr_audio_create")
         self._h = h
         self.nch, self.mode, self.width, self.device = nch, mode, width, device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_audio_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_audio_reset(self._h, _stream(stream)), "sdr_audio_reset")
 
     def set_control(self, blend=None, gain=None, stream=None):
         """New targets per channel (a scalar serves every channel): blend in [0, 1] (0 mono, 1 full
@@ -764,23 +737,18 @@ class AudioFinish:
 
     def state(self, stream=None):
         """numpy structured array [nch] of audio_state_dtype(); synchronises the stream."""
-        import numpy as np
-        out = np.zeros(self.nch, audio_state_dtype())
-        check(lib().sdr_audio_read_state(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_audio_read_state")
-        return out
+        return self._records("sdr_audio_read_state", audio_state_dtype(), stream)
 
 
 # ------------------------------------------------------------------ RDS group decoder (include/sdr_amd.h, sdr_rds_*)
 def rds_group_dtype():
     """numpy dtype of sdr_rds_group (16 bytes)."""
-    import numpy as np
-    return np.dtype(RdsGroup)
+    return _dtype(RdsGroup)
 
 
 def rds_stats_dtype():
     """numpy dtype of sdr_rds_stats (32 bytes)."""
-    import numpy as np
-    return np.dtype(RdsStats)
+    return _dtype(RdsStats)
 
 
 def rds_syndrome(w26: int) -> int:
@@ -800,39 +768,28 @@ def rds_correction_table(max_burst: int = 2):
 
 def rds_opts(**opts) -> RdsOpts:
     """The decoder's defaults (sdr_rds_opts_default) with the given fields replaced."""
-    o = RdsOpts()
-    lib().sdr_rds_opts_default(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(RdsOpts._fields_):
-            raise SdrError(f"rds_opts: unknown option {k}", -1)
-        setattr(o, k, v)
-    return o
+    return _opts(RdsOpts, "sdr_rds_opts_default", "rds_opts", **opts)
 
 
 def rds_soft_opts(**opts) -> RdsSoftOpts:
     """The soft decoder's defaults (sdr_rds_soft_opts_default) with the given fields replaced."""
-    o = RdsSoftOpts()
-    lib().sdr_rds_soft_opts_default(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(RdsSoftOpts._fields_):
-            raise SdrError(f"rds_soft_opts: unknown option {k}", -1)
-        setattr(o, k, v)
-    return o
+    return _opts(RdsSoftOpts, "sdr_rds_soft_opts_default", "rds_soft_opts", **opts)
 
 
 def rds_soft_stats_dtype():
     """numpy dtype of sdr_rds_soft_stats (16 bytes)."""
-    import numpy as np
-    return np.dtype(RdsSoftStats)
+    return _dtype(RdsSoftStats)
 
 
-class RdsDecoder:
+class RdsDecoder(_Handle):
     """The RDS group decoder of `nch` channels (sdr_rds_*): block sync with a flywheel, slip recovery and
     burst correction on the GPU. Per block feed(nbits, bits) or feed_pipeline(pipe) after the pipeline's
     rds(); groups() returns that call's group records. Its own handle; the state stays on the device.
     soft_bits > 0 (or soft=True, for a soft handle at soft_bits 0) makes a handle of sdr_rds_dec_create_soft:
     feed then needs the tracker's soft row, and a failing block is first searched over its soft_bits least
     reliable raw decisions."""
+
+    _destroy, _reset = "sdr_rds_dec_destroy", "sdr_rds_dec_reset"
 
     def __init__(self, nch: int, device: int = 0, max_burst: int = 2, loss_blocks: int = 8, soft_bits: int = 0,
                  soft: bool | None = None):
@@ -846,20 +803,6 @@ class RdsDecoder:
             check(lib().sdr_rds_dec_create(C.byref(h), device, nch, C.byref(o)), "sdr_rds_dec_create")
         self._h = h
         self.nch, self.device = nch, device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_rds_dec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_rds_dec_reset(self._h, _stream(stream)), "sdr_rds_dec_reset")
 
     def feed(self, nbits, bits, stream=None, soft=None):
         """One call: nbits int32 [nch] and bits uint8 [nch][>= SDR_MAX_BITS] device tensors; soft: the uint16
@@ -895,43 +838,30 @@ class RdsDecoder:
 
     def stats(self, stream=None):
         """numpy structured array [nch] of rds_stats_dtype(); synchronises the stream."""
-        import numpy as np
-        out = np.zeros(self.nch, rds_stats_dtype())
-        check(lib().sdr_rds_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_rds_stats_read")
-        return out
-
+        return self._records("sdr_rds_stats_read", rds_stats_dtype(), stream)
 
     def soft_stats(self, stream=None):
         """numpy structured array [nch] of rds_soft_stats_dtype(); synchronises the stream."""
-        import numpy as np
-        out = np.zeros(self.nch, rds_soft_stats_dtype())
-        check(lib().sdr_rds_soft_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)),
-              "sdr_rds_soft_stats_read")
-        return out
+        return self._records("sdr_rds_soft_stats_read", rds_soft_stats_dtype(), stream)
 
 
 def rds_track_stats_dtype():
     """numpy dtype of sdr_rds_track_stats (32 bytes)."""
-    import numpy as np
-    return np.dtype(RdsTrackStats)
+    return _dtype(RdsTrackStats)
 
 
 def rds_track_opts(**opts) -> RdsTrackOpts:
     """The tracker's defaults (sdr_rds_track_opts_default) with the given fields replaced."""
-    o = RdsTrackOpts()
-    lib().sdr_rds_track_opts_default(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(RdsTrackOpts._fields_):
-            raise SdrError(f"rds_track_opts: unknown option {k}", -1)
-        setattr(o, k, v)
-    return o
+    return _opts(RdsTrackOpts, "sdr_rds_track_opts_default", "rds_track_opts", **opts)
 
 
-class RdsTracker:
+class RdsTracker(_Handle):
     """The RDS symbol tracker of `nch` channels (sdr_rds_track_*): a bit clock carried from call to call and a
     biphase correlator over the whole bit, on the GPU. Per block feed(clean) or feed_pipeline(pipe) after the
     pipeline's rds(); the bits land in .nbits and .bits, in the layout RdsDecoder.feed takes. Mode 0 only.
     Its own handle; the state stays on the device."""
+
+    _destroy, _reset = "sdr_rds_track_destroy", "sdr_rds_track_reset"
 
     def __init__(self, nch: int, device: int = 0, mode: int = 0, **opts):
         import torch
@@ -944,20 +874,6 @@ class RdsTracker:
         self.nbits = torch.zeros(nch, dtype=torch.int32, device=dev)
         self.bits = torch.zeros(nch, SDR_MAX_BITS, dtype=torch.uint8, device=dev)
         self.soft = None                 # the reliabilities of .bits, allocated by the first feed(..., soft=True)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_rds_track_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_rds_track_reset(self._h, _stream(stream)), "sdr_rds_track_reset")
 
     def feed(self, clean, n: int | None = None, stream=None, nbits=None, bits=None, soft=None):
         """One call: clean is a float32 [nch][>= n] device tensor of rds_clean rows (n: its row length by
@@ -999,28 +915,17 @@ class RdsTracker:
 
     def stats(self, stream=None):
         """numpy structured array [nch] of rds_track_stats_dtype(); synchronises the stream."""
-        import numpy as np
-        out = np.zeros(self.nch, rds_track_stats_dtype())
-        check(lib().sdr_rds_track_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)),
-              "sdr_rds_track_stats_read")
-        return out
+        return self._records("sdr_rds_track_stats_read", rds_track_stats_dtype(), stream)
 
 
 def rds_carrier_stats_dtype():
     """numpy dtype of sdr_rds_carrier_stats (40 bytes)."""
-    import numpy as np
-    return np.dtype(RdsCarrierStats)
+    return _dtype(RdsCarrierStats)
 
 
 def rds_carrier_opts(**opts) -> RdsCarrierOpts:
     """The derotator's defaults (sdr_rds_carrier_opts_default) with the given fields replaced."""
-    o = RdsCarrierOpts()
-    lib().sdr_rds_carrier_opts_default(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(RdsCarrierOpts._fields_):
-            raise SdrError(f"rds_carrier_opts: unknown option {k}", -1)
-        setattr(o, k, v)
-    return o
+    return _opts(RdsCarrierOpts, "sdr_rds_carrier_opts_default", "rds_carrier_opts", **opts)
 
 
 def rds_carrier_phase_deg(stats):
@@ -1038,11 +943,13 @@ def rds_carrier_coherence(stats):
     return np.divide(h, st, out=np.zeros_like(h), where=st > 0)
 
 
-class RdsCarrier:
+class RdsCarrier(_Handle):
     """The RDS carrier-phase derotator of `nch` channels (sdr_rds_carrier_*): per call it turns the in-phase and
     quadrature rds_clean rows onto one axis by the phase of their squared signal, estimated window by window of
     the stream, on the GPU. feed(clean_i, clean_q) returns rows that RdsTracker.feed takes in place of rds_clean.
     Mode 0 only. Its own handle; the state stays on the device."""
+
+    _destroy, _reset = "sdr_rds_carrier_destroy", "sdr_rds_carrier_reset"
 
     def __init__(self, nch: int, device: int = 0, mode: int = 0, **opts):
         h = C.c_void_p()
@@ -1051,20 +958,6 @@ class RdsCarrier:
         self._h = h
         self.nch, self.device = nch, device
         self.out = None                  # the rotated rows, allocated by the first feed() that is given none
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_rds_carrier_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_rds_carrier_reset(self._h, _stream(stream)), "sdr_rds_carrier_reset")
 
     def feed(self, clean_i, clean_q, n: int | None = None, stream=None, out=None):
         """One call: clean_i and clean_q are float32 [nch][>= n] device tensors (n: the shorter row length by
@@ -1107,11 +1000,7 @@ class RdsCarrier:
 
     def stats(self, stream=None):
         """numpy structured array [nch] of rds_carrier_stats_dtype(); synchronises the stream."""
-        import numpy as np
-        out = np.zeros(self.nch, rds_carrier_stats_dtype())
-        check(lib().sdr_rds_carrier_stats_read(self._h, out.ctypes.data_as(C.c_void_p), _stream(stream)),
-              "sdr_rds_carrier_stats_read")
-        return out
+        return self._records("sdr_rds_carrier_stats_read", rds_carrier_stats_dtype(), stream)
 
 
 class RdsStation:
@@ -1236,11 +1125,13 @@ def pll_state_from_tensor(t) -> list:
 
 
 # ------------------------------------------------------------------ fused pipeline
-class Pipeline:
+class Pipeline(_Handle):
     """A device context of `nch` channels: the reference's RF_frontend + mono + stereo + rds bodies.
 
     Per block: frontend(iq) then any of mono(), stereo(), rds() (each at most once per block).
     """
+
+    _destroy, _reset = "sdr_ctx_destroy", "sdr_ctx_reset"
 
     def __init__(self, nch: int, mode: int = 0, rds_on: bool = True, device: int = 0, flags: int = 0):
         import torch
@@ -1260,20 +1151,6 @@ class Pipeline:
         self.nbits = torch.zeros(nch, dtype=i32, device=dev)
         self.symbols = torch.zeros(nch, SDR_MAX_SYMS, dtype=torch.uint8, device=dev)
         self.bits = torch.zeros(nch, SDR_MAX_BITS, dtype=torch.uint8, device=dev)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().sdr_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=None):
-        check(lib().sdr_ctx_reset(self._h, _stream(stream)), "sdr_ctx_reset")
 
     def frontend(self, iq, stream=None):
         """iq: uint8 [nch][2*block_iq] (device)."""

@@ -14,12 +14,11 @@
 //              over it)
 // with one barrier per tile; the chain never waits for global memory.
 // k_audio_blend, k_audio_control and k_audio_reset write the small per-channel state.
-#include "sdr_internal.h"
+#include "stage_host.h"
 
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -279,6 +278,22 @@ int sdr_audio_coeffs(int mode, float tau_us, float* a, float* b) {
     return coeffs(in, tau_us, a, b);
 }
 
+// the stage's rule for an options record in a mode (in); `who` names the caller in the text
+static int audio_opts_rule(const char* who, const sdr_info& in, const sdr_audio_opts* o, float* a, float* b) {
+    if (const int r = coeffs(in, o->tau_us, a, b)) return r;
+    if (!std::isfinite(o->blend_lo) || !std::isfinite(o->blend_hi) || !(o->blend_hi > o->blend_lo))
+        return fail(SDR_E_INVALID, "%s: blend_hi %g <= blend_lo %g", who, (double)o->blend_hi, (double)o->blend_lo);
+    return SDR_OK;
+}
+
+int sdr_audio_opts_check(int mode, const sdr_audio_opts* o) {
+    sdr_info in;
+    if (const int r = mode_info(&in, 1, mode, 1)) return r;
+    if (!o) return fail(SDR_E_INVALID, "audio_opts_check: opts is NULL");
+    float a = 0.0f, b = 1.0f;
+    return audio_opts_rule("audio_opts_check", in, o, &a, &b);
+}
+
 int sdr_audio_create(sdr_audio** out, int device, int nch, int mode, int width, const sdr_audio_opts* o) {
     if (!out) return fail(SDR_E_INVALID, "audio_create: out is NULL");
     *out = nullptr;
@@ -288,18 +303,14 @@ int sdr_audio_create(sdr_audio** out, int device, int nch, int mode, int width, 
     if (nch < 1) return fail(SDR_E_INVALID, "audio_create: nch %d < 1", nch);
     if (width != 1 && width != 2) return fail(SDR_E_INVALID, "audio_create: width %d is not 1 or 2", width);
     float ca = 0.0f, cb = 1.0f;
-    if (const int r = coeffs(in, o->tau_us, &ca, &cb)) return r;
-    if (!std::isfinite(o->blend_lo) || !std::isfinite(o->blend_hi) || !(o->blend_hi > o->blend_lo))
-        return fail(SDR_E_INVALID, "audio_create: blend_hi %g <= blend_lo %g", (double)o->blend_hi, (double)o->blend_lo);
+    if (const int r = audio_opts_rule("audio_create", in, o, &ca, &cb)) return r;
     int shape = 2;   // 8 channels per workgroup (4 measured 9 % faster alone: DESIGN 4e)
     if (const char* e = std::getenv("SDR_AUDIO_SHAPE")) {   // for A/B (tools/bench_audio.py)
         shape = std::atoi(e);
         if (shape < 0 || shape >= SHAPES) return fail(SDR_E_INVALID, "audio_create: SDR_AUDIO_SHAPE %s", e);
     }
-    HIP_TRY(hipSetDevice(device));
-    sdr_audio* a = new (std::nothrow) sdr_audio;
-    if (!a) return fail(SDR_E_NOMEM, "audio_create: out of memory");
-    a->device = device;
+    sdr_audio* a = nullptr;
+    if (const int r = create_begin(&a, device, "audio_create")) return r;
     a->nch = nch;
     a->mode = mode;
     a->width = width;
@@ -310,20 +321,12 @@ int sdr_audio_create(sdr_audio** out, int device, int nch, int mode, int width, 
     a->b = cb;
     a->lo = o->blend_lo;
     a->hi = o->blend_hi;
-    hipError_t e = hipMalloc((void**)&a->st, (size_t)nch * sizeof(sdr_audio_state));
+    hipError_t e = hipSuccess;
+    dev_alloc(e, &a->st, (size_t)nch * sizeof(sdr_audio_state));
     if (e == hipSuccess) e = hipHostMalloc((void**)&a->ctl, (size_t)2 * nch * sizeof(float), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ctl_read, hipEventDisableTiming);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_audio_reset, dim3((nch + 255) / 256), dim3(256), 0, nullptr, a->st, nch);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        sdr_audio_destroy(a);
-        return fail(e == hipErrorOutOfMemory ? SDR_E_NOMEM : SDR_E_HIP, "audio_create: %s", hipGetErrorString(e));
-    }
-    *out = a;
-    return SDR_OK;
+    create_reset(e, k_audio_reset, groups256(nch), a->st, nch);
+    return create_done(e, a, out, sdr_audio_destroy, "audio_create");
 }
 
 int sdr_audio_destroy(sdr_audio* a) {
@@ -339,10 +342,7 @@ int sdr_audio_destroy(sdr_audio* a) {
 
 int sdr_audio_reset(sdr_audio* a, void* stream) {
     if (!a) return fail(SDR_E_INVALID, "audio_reset: null handle");
-    HIP_TRY(hipSetDevice(a->device));
-    hipLaunchKernelGGL(k_audio_reset, dim3((a->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->st, a->nch);
-    LAUNCH_CHECK();
-    return SDR_OK;
+    return launch_on(a->device, k_audio_reset, groups256(a->nch), S(stream), a->st, a->nch);
 }
 
 int sdr_audio_set_control(sdr_audio* a, const float* blend, const float* gain, void* stream) {
@@ -373,11 +373,8 @@ int sdr_audio_blend_from_meter(sdr_audio* a, sdr_meter* m, void* stream) {
     if (m->nch != a->nch || m->mode != a->mode || m->device != a->device)
         return fail(SDR_E_INVALID, "audio_blend_from_meter: the meter (nch %d, mode %d, device %d) is not the stage's (%d, %d, %d)",
                     m->nch, m->mode, m->device, a->nch, a->mode, a->device);
-    HIP_TRY(hipSetDevice(a->device));
-    hipLaunchKernelGGL(k_audio_blend, dim3((a->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream, m->rows, a->st, a->nch,
-                       (float)a->block_if, (float)(a->block_if / 5), a->lo, a->hi - a->lo);
-    LAUNCH_CHECK();
-    return SDR_OK;
+    return launch_on(a->device, k_audio_blend, groups256(a->nch), S(stream), m->rows, a->st, a->nch, (float)a->block_if,
+                     (float)(a->block_if / 5), a->lo, a->hi - a->lo);
 }
 
 int sdr_audio_finish(sdr_audio* a, const int16_t* in, size_t in_stride, int16_t* out, size_t out_stride, void* stream) {
@@ -408,9 +405,7 @@ int sdr_audio_finish(sdr_audio* a, const int16_t* in, size_t in_stride, int16_t*
 int sdr_audio_read_state(sdr_audio* a, sdr_audio_state* host, void* stream) {
     if (!a || !host) return fail(SDR_E_INVALID, "audio_read_state: null argument");
     HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipMemcpyAsync(host, a->st, (size_t)a->nch * sizeof(sdr_audio_state), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return SDR_OK;
+    return copy_records(a->st, host, a->nch, S(stream));
 }
 
 }  // extern "C"

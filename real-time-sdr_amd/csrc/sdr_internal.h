@@ -8,6 +8,7 @@
 //   sdr_streams.hip    CU-masked streams and their placement, per-stream scratch, sdr_hbm_copy, test hooks
 //   sdr_primitives.hip the context-free primitives (FIR, resampler, demod, fmpll, cdr, bit decoders)
 //   stage_device.h     device code shared by sdr_kernels.hip and sdr_primitives.hip
+//   stage_host.h       host code shared by the units below that own a handle: create, destroy, reset, record reads
 //   sdr_scan.hip       band scan of the capture rows
 //   sdr_meter.hip      reception meter: per-channel readings of a block's rows
 //   sdr_split.hip      wideband splitter: a wide s8 capture into the capture rows (its own handle)

@@ -1259,23 +1259,36 @@ int sdr_frontend(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* stream) 
 }
 
 // ---- shared-capture tuner: channel ch = source row src[ch] shifted by khz[ch] kHz (sdr_frontend.hip)
+// the rule for a tuning of nch channels at N = rf_Fs / 1000 (nsrc = 0: untuned); `who` names the caller in the text
+static int tuner_rule(const char* who, int N, int nch, int nsrc, const int32_t* src, const int32_t* khz) {
+    if (nsrc < 0 || nsrc > nch) return fail(SDR_E_INVALID, "%s: nsrc %d outside [0, nch %d]", who, nsrc, nch);
+    if (nsrc == 0) return SDR_OK;
+    if (!src || !khz) return fail(SDR_E_INVALID, "%s: null src or khz", who);
+    for (int ch = 0; ch < nch; ch++) {
+        if (src[ch] < 0 || src[ch] >= nsrc)
+            return fail(SDR_E_INVALID, "%s: src[%d] = %d outside [0, %d)", who, ch, (int)src[ch], nsrc);
+        if (2 * (long long)khz[ch] <= -(long long)N || 2 * (long long)khz[ch] > N)
+            return fail(SDR_E_INVALID, "%s: khz[%d] = %d outside (-%d/2, %d/2]", who, ch, (int)khz[ch], N, N);
+    }
+    return SDR_OK;
+}
+
+int sdr_tuner_check(int mode, int nch, int nsrc, const int32_t* src, const int32_t* khz) {
+    sdr_info in;
+    if (const int r = mode_info(&in, nch, mode, 1)) return r;
+    return tuner_rule("tuner_check", in.rf_Fs / 1000, nch, nsrc, src, khz);
+}
+
 int sdr_tuner_set(sdr_ctx* c, int nsrc, const int32_t* src, const int32_t* khz, void* stream) {
     if (!c) return fail(SDR_E_INVALID, "tuner_set: null context");
     if (c->block != -1) return fail(SDR_E_INVALID, "tuner_set: only at block 0 (after create or sdr_ctx_reset)");
     if (!c->tn_tab) return fail(SDR_E_INVALID, "tuner_set: the context has no tuned front end");
-    if (nsrc < 0 || nsrc > c->nch) return fail(SDR_E_INVALID, "tuner_set: nsrc %d outside [0, nch %d]", nsrc, c->nch);
+    const int N = c->info.rf_Fs / 1000;
+    if (const int r = tuner_rule("tuner_set", N, c->nch, nsrc, src, khz)) return r;
     c->fe_time.cap = c->fe_time.n = 0;   // (the timed launches' stamp layout belongs to the other kernel)
     if (nsrc == 0) {
         c->tn_nsrc = 0;
         return SDR_OK;
-    }
-    if (!src || !khz) return fail(SDR_E_INVALID, "tuner_set: null src or khz");
-    const int N = c->info.rf_Fs / 1000;
-    for (int ch = 0; ch < c->nch; ch++) {
-        if (src[ch] < 0 || src[ch] >= nsrc)
-            return fail(SDR_E_INVALID, "tuner_set: src[%d] = %d outside [0, %d)", ch, (int)src[ch], nsrc);
-        if (2 * (long long)khz[ch] <= -(long long)N || 2 * (long long)khz[ch] > N)
-            return fail(SDR_E_INVALID, "tuner_set: khz[%d] = %d outside (-%d/2, %d/2]", ch, (int)khz[ch], N, N);
     }
     // grid order: channels sorted by source row (stable), so the stations of a row are neighbours;
     // the first of each row stores the row's tail

@@ -20,10 +20,9 @@
 //
 // A channel's row is written by one workgroup with plain stores, each call its own fields; the flags
 // word alone is shared by the two calls (which may run on two streams), so each ORs its bit in.
-#include "sdr_internal.h"
+#include "stage_host.h"
 
 #include <cmath>
-#include <new>
 
 #pragma clang fp contract(off)
 
@@ -325,32 +324,21 @@ int sdr_meter_create(sdr_meter** out, int device, int nch, int mode) {
     float h[NOISE_T];
     int nt = 0;
     if (const int r = sdr_meter_taps(mode, h, NOISE_T, &nt)) return r;
-    HIP_TRY(hipSetDevice(device));
-    sdr_meter* m = new (std::nothrow) sdr_meter;
-    if (!m) return fail(SDR_E_NOMEM, "meter_create: out of memory");
-    m->device = device;
+    sdr_meter* m = nullptr;
+    if (const int r = create_begin(&m, device, "meter_create")) return r;
     m->nch = nch;
     m->mode = mode;
-    hipError_t e = hipMalloc((void**)&m->h, sizeof(h));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->rows, (size_t)nch * sizeof(sdr_meter_row));
+    hipError_t e = hipSuccess;
+    dev_alloc(e, &m->h, sizeof(h));
+    dev_alloc(e, &m->rows, (size_t)nch * sizeof(sdr_meter_row));
     if (e == hipSuccess) e = hipMemcpy(m->h, h, sizeof(h), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(m->rows, 0, (size_t)nch * sizeof(sdr_meter_row));
-    if (e != hipSuccess) {
-        sdr_meter_destroy(m);
-        return fail(e == hipErrorOutOfMemory ? SDR_E_NOMEM : SDR_E_HIP, "meter_create: %s", hipGetErrorString(e));
-    }
-    *out = m;
-    return SDR_OK;
+    return create_done(e, m, out, sdr_meter_destroy, "meter_create");
 }
 
 int sdr_meter_destroy(sdr_meter* m) {
     if (!m) return fail(SDR_E_INVALID, "meter_destroy: null meter");
-    (void)hipSetDevice(m->device);
-    (void)hipDeviceSynchronize();   // a pending call may still write the rows
-    if (m->h) (void)hipFree(m->h);
-    if (m->rows) (void)hipFree(m->rows);
-    delete m;
-    return SDR_OK;
+    return destroy_handle(m, {m->h, m->rows});
 }
 
 int sdr_meter_reset(sdr_meter* m, void* stream) {
@@ -420,10 +408,7 @@ int sdr_meter_rds(sdr_meter* m, sdr_ctx* c, void* stream) {
 int sdr_meter_read(sdr_meter* m, sdr_meter_row* host_rows, void* stream) {
     if (!m || !host_rows) return fail(SDR_E_INVALID, "meter_read: null argument");
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpyAsync(host_rows, m->rows, (size_t)m->nch * sizeof(sdr_meter_row), hipMemcpyDeviceToHost,
-                           (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return SDR_OK;
+    return copy_records(m->rows, host_rows, m->nch, S(stream));
 }
 
 int sdr_meter_rows(sdr_meter* m, const sdr_meter_row** dev) {

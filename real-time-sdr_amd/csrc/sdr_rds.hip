@@ -14,10 +14,9 @@
 //             All that it reads is the absolute state, so the cut of the stream into calls does not matter.
 // The state is one 128-byte record per channel in HBM, written back by lane 0 with plain vector stores;
 // the correction table (1024 x u32) is read on the failing-block path only.
-#include "sdr_internal.h"
+#include "stage_host.h"
 
 #include <cstring>
-#include <new>
 
 struct sdr_rds_dec {
     int device = 0, nch = 0, max_burst = 0, loss_blocks = 0;
@@ -428,48 +427,56 @@ void sdr_rds_soft_opts_default(sdr_rds_soft_opts* o) {
     o->soft_bits = 6;
 }
 
+// the rules of the options records; `who` names the caller in the text
+static int opts_rule(const char* who, int max_burst, int loss_blocks) {
+    if (max_burst < 0 || max_burst > 5) return fail(SDR_E_INVALID, "%s: max_burst %d is not in 0..5", who, max_burst);
+    if (loss_blocks < 1 || loss_blocks > 64) return fail(SDR_E_INVALID, "%s: loss_blocks %d is not in 1..64", who, loss_blocks);
+    return SDR_OK;
+}
+static int soft_bits_rule(const char* who, int soft_bits) {
+    if (soft_bits < 0 || soft_bits > 6) return fail(SDR_E_INVALID, "%s: soft_bits %d is not in 0..6", who, soft_bits);
+    return SDR_OK;
+}
+
+int sdr_rds_opts_check(const sdr_rds_opts* opts) {
+    if (!opts) return fail(SDR_E_INVALID, "rds_opts_check: opts is NULL");
+    return opts_rule("rds_opts_check", opts->max_burst, opts->loss_blocks);
+}
+
+int sdr_rds_soft_opts_check(const sdr_rds_soft_opts* opts) {
+    if (!opts) return fail(SDR_E_INVALID, "rds_soft_opts_check: opts is NULL");
+    if (const int r = soft_bits_rule("rds_soft_opts_check", opts->soft_bits)) return r;
+    return opts_rule("rds_soft_opts_check", opts->max_burst, opts->loss_blocks);
+}
+
 // soft_bits < 0: a handle of sdr_rds_dec_create
 static int dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opts* opts, int soft_bits) {
     if (!out) return fail(SDR_E_INVALID, "rds_dec_create: out is NULL");
     *out = nullptr;
     if (!opts) return fail(SDR_E_INVALID, "rds_dec_create: opts is NULL");
     if (nch < 1) return fail(SDR_E_INVALID, "rds_dec_create: nch %d < 1", nch);
-    if (opts->max_burst < 0 || opts->max_burst > 5)
-        return fail(SDR_E_INVALID, "rds_dec_create: max_burst %d is not in 0..5", opts->max_burst);
-    if (opts->loss_blocks < 1 || opts->loss_blocks > 64)
-        return fail(SDR_E_INVALID, "rds_dec_create: loss_blocks %d is not in 1..64", opts->loss_blocks);
+    if (const int r = opts_rule("rds_dec_create", opts->max_burst, opts->loss_blocks)) return r;
     uint32_t tab[1024];
     if (sdr_rds_correction_table(opts->max_burst, tab, nullptr) != SDR_OK)
         return fail(SDR_E_INVALID, "rds_dec_create: no correction table");
-    HIP_TRY(hipSetDevice(device));
-    sdr_rds_dec* d = new (std::nothrow) sdr_rds_dec;
-    if (!d) return fail(SDR_E_NOMEM, "rds_dec_create: out of memory");
-    d->device = device;
+    sdr_rds_dec* d = nullptr;
+    if (const int r = create_begin(&d, device, "rds_dec_create")) return r;
     d->nch = nch;
     d->max_burst = opts->max_burst;
     d->loss_blocks = opts->loss_blocks;
     d->soft = soft_bits >= 0;
     d->soft_bits = soft_bits >= 0 ? soft_bits : 0;
-    hipError_t e = hipMalloc(&d->st, (size_t)nch * sizeof(RdsState));
-    if (e == hipSuccess && d->soft) e = hipMalloc((void**)&d->hist, (size_t)nch * SOFT_HIST * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d->sstats, (size_t)nch * sizeof(sdr_rds_soft_stats));
-    if (e == hipSuccess) e = hipMalloc((void**)&d->tab, sizeof tab);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->groups, (size_t)nch * SDR_RDS_MAX_GROUPS * sizeof(sdr_rds_group));
-    if (e == hipSuccess) e = hipMalloc((void**)&d->ngroups, (size_t)nch * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d->stats, (size_t)nch * sizeof(sdr_rds_stats));
+    hipError_t e = hipSuccess;
+    dev_alloc(e, &d->st, (size_t)nch * sizeof(RdsState));
+    if (d->soft) dev_alloc(e, &d->hist, (size_t)nch * SOFT_HIST * sizeof(uint16_t));
+    dev_alloc(e, &d->sstats, (size_t)nch * sizeof(sdr_rds_soft_stats));
+    dev_alloc(e, &d->tab, sizeof tab);
+    dev_alloc(e, &d->groups, (size_t)nch * SDR_RDS_MAX_GROUPS * sizeof(sdr_rds_group));
+    dev_alloc(e, &d->ngroups, (size_t)nch * sizeof(int32_t));
+    dev_alloc(e, &d->stats, (size_t)nch * sizeof(sdr_rds_stats));
     if (e == hipSuccess) e = hipMemcpy(d->tab, tab, sizeof tab, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_rds_reset, dim3((nch + 255) / 256), dim3(256), 0, nullptr, (RdsState*)d->st, d->groups,
-                           d->ngroups, nch, d->hist);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        sdr_rds_dec_destroy(d);
-        return fail(e == hipErrorOutOfMemory ? SDR_E_NOMEM : SDR_E_HIP, "rds_dec_create: %s", hipGetErrorString(e));
-    }
-    *out = d;
-    return SDR_OK;
+    create_reset(e, k_rds_reset, groups256(nch), d->st, d->groups, d->ngroups, nch, d->hist);
+    return create_done(e, d, out, sdr_rds_dec_destroy, "rds_dec_create");
 }
 
 int sdr_rds_dec_create(sdr_rds_dec** out, int device, int nch, const sdr_rds_opts* opts) {
@@ -480,34 +487,19 @@ int sdr_rds_dec_create_soft(sdr_rds_dec** out, int device, int nch, const sdr_rd
     if (!out) return fail(SDR_E_INVALID, "rds_dec_create_soft: out is NULL");
     *out = nullptr;
     if (!opts) return fail(SDR_E_INVALID, "rds_dec_create_soft: opts is NULL");
-    if (opts->soft_bits < 0 || opts->soft_bits > 6)
-        return fail(SDR_E_INVALID, "rds_dec_create_soft: soft_bits %d is not in 0..6", opts->soft_bits);
+    if (const int r = soft_bits_rule("rds_dec_create_soft", opts->soft_bits)) return r;
     const sdr_rds_opts ro{opts->max_burst, opts->loss_blocks};
     return dec_create(out, device, nch, &ro, opts->soft_bits);
 }
 
 int sdr_rds_dec_destroy(sdr_rds_dec* d) {
     if (!d) return fail(SDR_E_INVALID, "rds_dec_destroy: null handle");
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();   // a pending call may still use the state
-    if (d->st) (void)hipFree(d->st);
-    if (d->tab) (void)hipFree(d->tab);
-    if (d->groups) (void)hipFree(d->groups);
-    if (d->ngroups) (void)hipFree(d->ngroups);
-    if (d->stats) (void)hipFree(d->stats);
-    if (d->hist) (void)hipFree(d->hist);
-    if (d->sstats) (void)hipFree(d->sstats);
-    delete d;
-    return SDR_OK;
+    return destroy_handle(d, {d->st, d->tab, d->groups, d->ngroups, d->stats, d->hist, d->sstats});
 }
 
 int sdr_rds_dec_reset(sdr_rds_dec* d, void* stream) {
     if (!d) return fail(SDR_E_INVALID, "rds_dec_reset: null handle");
-    HIP_TRY(hipSetDevice(d->device));
-    hipLaunchKernelGGL(k_rds_reset, dim3((d->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream, (RdsState*)d->st,
-                       d->groups, d->ngroups, d->nch, d->hist);
-    LAUNCH_CHECK();
-    return SDR_OK;
+    return launch_on(d->device, k_rds_reset, groups256(d->nch), S(stream), d->st, d->groups, d->ngroups, d->nch, d->hist);
 }
 
 int sdr_rds_groups(sdr_rds_dec* d, const int32_t* nbits_dev, const uint8_t* bits_dev, size_t bits_stride, void* stream) {
@@ -560,26 +552,15 @@ int sdr_rds_groups_read(sdr_rds_dec* d, sdr_rds_group* host_groups, int32_t* hos
 
 int sdr_rds_stats_read(sdr_rds_dec* d, sdr_rds_stats* host_stats, void* stream) {
     if (!d || !host_stats) return fail(SDR_E_INVALID, "rds_stats_read: null argument");
-    HIP_TRY(hipSetDevice(d->device));
-    hipLaunchKernelGGL(k_rds_stats, dim3((d->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const RdsState*)d->st,
-                       d->stats, d->nch);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(host_stats, d->stats, (size_t)d->nch * sizeof(sdr_rds_stats), hipMemcpyDeviceToHost,
-                           (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return SDR_OK;
+    if (const int r = launch_on(d->device, k_rds_stats, groups256(d->nch), S(stream), d->st, d->stats, d->nch)) return r;
+    return copy_records(d->stats, host_stats, d->nch, S(stream));
 }
 
 int sdr_rds_soft_stats_read(sdr_rds_dec* d, sdr_rds_soft_stats* host_stats, void* stream) {
     if (!d || !host_stats) return fail(SDR_E_INVALID, "rds_soft_stats_read: null argument");
-    HIP_TRY(hipSetDevice(d->device));
-    hipLaunchKernelGGL(k_rds_soft_stats, dim3((d->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       (const RdsState*)d->st, d->sstats, d->nch, d->soft_bits);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(host_stats, d->sstats, (size_t)d->nch * sizeof(sdr_rds_soft_stats), hipMemcpyDeviceToHost,
-                           (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return SDR_OK;
+    if (const int r = launch_on(d->device, k_rds_soft_stats, groups256(d->nch), S(stream), d->st, d->sstats, d->nch, d->soft_bits))
+        return r;
+    return copy_records(d->sstats, host_stats, d->nch, S(stream));
 }
 
 }  // extern "C"

@@ -16,10 +16,9 @@
 // not depend on how the stream is cut, so that is the same result.
 // The state is one 128-byte record per channel in HBM, read by every lane and written back by lane 0 with
 // plain vector stores.
-#include "sdr_internal.h"
+#include "stage_host.h"
 
 #include <cstring>
-#include <new>
 
 struct sdr_rds_carrier {
     int device = 0, nch = 0, mode = 0;
@@ -253,53 +252,45 @@ void sdr_rds_carrier_opts_default(sdr_rds_carrier_opts* o) {
     o->avg_shift = 3;
 }
 
+// the derotator's rule for a mode and an options record; `who` names the caller in the text
+static int carrier_opts_rule(const char* who, int mode, const sdr_rds_carrier_opts* opts) {
+    if (!sdr_rds_mode_ok(mode)) return fail(SDR_E_INVALID, "%s: mode %d has no RDS chain to derotate", who, mode);
+    if (opts->qshift < 0 || opts->qshift > 15) return fail(SDR_E_INVALID, "%s: qshift %d is not in 0..15", who, opts->qshift);
+    if (opts->avg_shift < 0 || opts->avg_shift > 6)
+        return fail(SDR_E_INVALID, "%s: avg_shift %d is not in 0..6", who, opts->avg_shift);
+    return SDR_OK;
+}
+
+int sdr_rds_carrier_opts_check(int mode, const sdr_rds_carrier_opts* opts) {
+    if (!opts) return fail(SDR_E_INVALID, "rds_carrier_opts_check: opts is NULL");
+    return carrier_opts_rule("rds_carrier_opts_check", mode, opts);
+}
+
 int sdr_rds_carrier_create(sdr_rds_carrier** out, int device, int nch, int mode, const sdr_rds_carrier_opts* opts) {
     if (!out) return fail(SDR_E_INVALID, "rds_carrier_create: out is NULL");
     *out = nullptr;
     if (!opts) return fail(SDR_E_INVALID, "rds_carrier_create: opts is NULL");
     if (nch < 1) return fail(SDR_E_INVALID, "rds_carrier_create: nch %d < 1", nch);
-    if (!sdr_rds_mode_ok(mode)) return fail(SDR_E_INVALID, "rds_carrier_create: mode %d has no RDS chain to derotate", mode);
-    if (opts->qshift < 0 || opts->qshift > 15)
-        return fail(SDR_E_INVALID, "rds_carrier_create: qshift %d is not in 0..15", opts->qshift);
-    if (opts->avg_shift < 0 || opts->avg_shift > 6)
-        return fail(SDR_E_INVALID, "rds_carrier_create: avg_shift %d is not in 0..6", opts->avg_shift);
-    HIP_TRY(hipSetDevice(device));
-    sdr_rds_carrier* h = new (std::nothrow) sdr_rds_carrier;
-    if (!h) return fail(SDR_E_NOMEM, "rds_carrier_create: out of memory");
-    h->device = device, h->nch = nch, h->mode = mode;
+    if (const int r = carrier_opts_rule("rds_carrier_create", mode, opts)) return r;
+    sdr_rds_carrier* h = nullptr;
+    if (const int r = create_begin(&h, device, "rds_carrier_create")) return r;
+    h->nch = nch, h->mode = mode;
     h->opts = *opts;
-    hipError_t e = hipMalloc(&h->st, (size_t)nch * sizeof(CarState));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->stats, (size_t)nch * sizeof(sdr_rds_carrier_stats));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_carrier_reset, dim3((nch + 255) / 256), dim3(256), 0, nullptr, (CarState*)h->st, nch);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        sdr_rds_carrier_destroy(h);
-        return fail(e == hipErrorOutOfMemory ? SDR_E_NOMEM : SDR_E_HIP, "rds_carrier_create: %s", hipGetErrorString(e));
-    }
-    *out = h;
-    return SDR_OK;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, &h->st, (size_t)nch * sizeof(CarState));
+    dev_alloc(e, &h->stats, (size_t)nch * sizeof(sdr_rds_carrier_stats));
+    create_reset(e, k_carrier_reset, groups256(nch), h->st, nch);
+    return create_done(e, h, out, sdr_rds_carrier_destroy, "rds_carrier_create");
 }
 
 int sdr_rds_carrier_destroy(sdr_rds_carrier* h) {
     if (!h) return fail(SDR_E_INVALID, "rds_carrier_destroy: null handle");
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();   // a pending call may still use the state
-    if (h->st) (void)hipFree(h->st);
-    if (h->stats) (void)hipFree(h->stats);
-    delete h;
-    return SDR_OK;
+    return destroy_handle(h, {h->st, h->stats});
 }
 
 int sdr_rds_carrier_reset(sdr_rds_carrier* h, void* stream) {
     if (!h) return fail(SDR_E_INVALID, "rds_carrier_reset: null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_carrier_reset, dim3((h->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream, (CarState*)h->st,
-                       h->nch);
-    LAUNCH_CHECK();
-    return SDR_OK;
+    return launch_on(h->device, k_carrier_reset, groups256(h->nch), S(stream), h->st, h->nch);
 }
 
 int sdr_rds_carrier_rotate(sdr_rds_carrier* h, const float* clean_i, size_t stride_i, const float* clean_q,
@@ -326,14 +317,8 @@ int sdr_rds_carrier_rotate(sdr_rds_carrier* h, const float* clean_i, size_t stri
 
 int sdr_rds_carrier_stats_read(sdr_rds_carrier* h, sdr_rds_carrier_stats* host_stats, void* stream) {
     if (!h || !host_stats) return fail(SDR_E_INVALID, "rds_carrier_stats_read: null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_carrier_stats, dim3((h->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       (const CarState*)h->st, h->stats, h->nch);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(host_stats, h->stats, (size_t)h->nch * sizeof(sdr_rds_carrier_stats), hipMemcpyDeviceToHost,
-                           (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return SDR_OK;
+    if (const int r = launch_on(h->device, k_carrier_stats, groups256(h->nch), S(stream), h->st, h->stats, h->nch)) return r;
+    return copy_records(h->stats, host_stats, h->nch, S(stream));
 }
 
 }  // extern "C"

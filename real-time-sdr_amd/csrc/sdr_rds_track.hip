@@ -19,10 +19,9 @@
 // not depend on how the stream is cut, so that is the same result.
 // The state is one 640-byte record per channel in HBM; lane 0 writes the scalars back, the lanes the carry
 // and the accumulators they own, all with plain vector stores.
-#include "sdr_internal.h"
+#include "stage_host.h"
 
 #include <cstring>
-#include <new>
 
 struct sdr_rds_track {
     int device = 0, nch = 0, mode = 0, S = 0;
@@ -325,58 +324,52 @@ void sdr_rds_track_opts_default(sdr_rds_track_opts* o) {
     o->half_bits = 64;
 }
 
+// the tracker's rule for a mode and an options record; `who` names the caller in the text
+static int track_opts_rule(const char* who, int mode, const sdr_rds_track_opts* opts, sdr_info* in) {
+    if (!sdr_rds_mode_ok(mode)) return fail(SDR_E_INVALID, "%s: mode %d has no 1187.5 bit/s clock", who, mode);
+    if (opts->qshift < 0 || opts->qshift > 15) return fail(SDR_E_INVALID, "%s: qshift %d is not in 0..15", who, opts->qshift);
+    if (opts->acquire_bits < 1 || opts->acquire_bits > 64)
+        return fail(SDR_E_INVALID, "%s: acquire_bits %d is not in 1..64", who, opts->acquire_bits);
+    if (opts->half_bits < SDR_RDS_TRACK_T || opts->half_bits > 64 || opts->half_bits % SDR_RDS_TRACK_T)
+        return fail(SDR_E_INVALID, "%s: half_bits %d is not a multiple of %d in %d..64", who, opts->half_bits,
+                    SDR_RDS_TRACK_T, SDR_RDS_TRACK_T);
+    if (mode_info(in, 1, mode, 1) != SDR_OK || in->symbol_Fs != TRK_S)
+        return fail(SDR_E_INVALID, "%s: mode %d is not at %d samples a chip", who, mode, TRK_S);
+    return SDR_OK;
+}
+
+int sdr_rds_track_opts_check(int mode, const sdr_rds_track_opts* opts) {
+    if (!opts) return fail(SDR_E_INVALID, "rds_track_opts_check: opts is NULL");
+    sdr_info in;
+    return track_opts_rule("rds_track_opts_check", mode, opts, &in);
+}
+
 int sdr_rds_track_create(sdr_rds_track** out, int device, int nch, int mode, const sdr_rds_track_opts* opts) {
     if (!out) return fail(SDR_E_INVALID, "rds_track_create: out is NULL");
     *out = nullptr;
     if (!opts) return fail(SDR_E_INVALID, "rds_track_create: opts is NULL");
     if (nch < 1) return fail(SDR_E_INVALID, "rds_track_create: nch %d < 1", nch);
-    if (!sdr_rds_mode_ok(mode)) return fail(SDR_E_INVALID, "rds_track_create: mode %d has no 1187.5 bit/s clock", mode);
-    if (opts->qshift < 0 || opts->qshift > 15)
-        return fail(SDR_E_INVALID, "rds_track_create: qshift %d is not in 0..15", opts->qshift);
-    if (opts->acquire_bits < 1 || opts->acquire_bits > 64)
-        return fail(SDR_E_INVALID, "rds_track_create: acquire_bits %d is not in 1..64", opts->acquire_bits);
-    if (opts->half_bits < SDR_RDS_TRACK_T || opts->half_bits > 64 || opts->half_bits % SDR_RDS_TRACK_T)
-        return fail(SDR_E_INVALID, "rds_track_create: half_bits %d is not a multiple of %d in %d..64", opts->half_bits,
-                    SDR_RDS_TRACK_T, SDR_RDS_TRACK_T);
     sdr_info in;
-    if (mode_info(&in, 1, mode, 1) != SDR_OK || in.symbol_Fs != TRK_S)
-        return fail(SDR_E_INVALID, "rds_track_create: mode %d is not at %d samples a chip", mode, TRK_S);
-    HIP_TRY(hipSetDevice(device));
-    sdr_rds_track* t = new (std::nothrow) sdr_rds_track;
-    if (!t) return fail(SDR_E_NOMEM, "rds_track_create: out of memory");
-    t->device = device, t->nch = nch, t->mode = mode, t->S = in.symbol_Fs;
+    if (const int r = track_opts_rule("rds_track_create", mode, opts, &in)) return r;
+    sdr_rds_track* t = nullptr;
+    if (const int r = create_begin(&t, device, "rds_track_create")) return r;
+    t->nch = nch, t->mode = mode, t->S = in.symbol_Fs;
     t->opts = *opts;
-    hipError_t e = hipMalloc(&t->st, (size_t)nch * sizeof(TrackState));
-    if (e == hipSuccess) e = hipMalloc((void**)&t->stats, (size_t)nch * sizeof(sdr_rds_track_stats));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_track_reset, dim3(reset_grid(nch)), dim3(256), 0, nullptr, (TrackState*)t->st, nch);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        sdr_rds_track_destroy(t);
-        return fail(e == hipErrorOutOfMemory ? SDR_E_NOMEM : SDR_E_HIP, "rds_track_create: %s", hipGetErrorString(e));
-    }
-    *out = t;
-    return SDR_OK;
+    hipError_t e = hipSuccess;
+    dev_alloc(e, &t->st, (size_t)nch * sizeof(TrackState));
+    dev_alloc(e, &t->stats, (size_t)nch * sizeof(sdr_rds_track_stats));
+    create_reset(e, k_track_reset, reset_grid(nch), t->st, nch);
+    return create_done(e, t, out, sdr_rds_track_destroy, "rds_track_create");
 }
 
 int sdr_rds_track_destroy(sdr_rds_track* t) {
     if (!t) return fail(SDR_E_INVALID, "rds_track_destroy: null handle");
-    (void)hipSetDevice(t->device);
-    (void)hipDeviceSynchronize();   // a pending call may still use the state
-    if (t->st) (void)hipFree(t->st);
-    if (t->stats) (void)hipFree(t->stats);
-    delete t;
-    return SDR_OK;
+    return destroy_handle(t, {t->st, t->stats});
 }
 
 int sdr_rds_track_reset(sdr_rds_track* t, void* stream) {
     if (!t) return fail(SDR_E_INVALID, "rds_track_reset: null handle");
-    HIP_TRY(hipSetDevice(t->device));
-    hipLaunchKernelGGL(k_track_reset, dim3(reset_grid(t->nch)), dim3(256), 0, (hipStream_t)stream, (TrackState*)t->st, t->nch);
-    LAUNCH_CHECK();
-    return SDR_OK;
+    return launch_on(t->device, k_track_reset, reset_grid(t->nch), S(stream), t->st, t->nch);
 }
 
 static int track_call(sdr_rds_track* t, const float* clean_dev, size_t clean_stride, int n, int32_t* nbits_dev,
@@ -424,14 +417,8 @@ int sdr_rds_track_bits_soft(sdr_rds_track* t, const float* clean_dev, size_t cle
 
 int sdr_rds_track_stats_read(sdr_rds_track* t, sdr_rds_track_stats* host_stats, void* stream) {
     if (!t || !host_stats) return fail(SDR_E_INVALID, "rds_track_stats_read: null argument");
-    HIP_TRY(hipSetDevice(t->device));
-    hipLaunchKernelGGL(k_track_stats, dim3((t->nch + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       (const TrackState*)t->st, t->stats, t->nch);
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(host_stats, t->stats, (size_t)t->nch * sizeof(sdr_rds_track_stats), hipMemcpyDeviceToHost,
-                           (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return SDR_OK;
+    if (const int r = launch_on(t->device, k_track_stats, groups256(t->nch), S(stream), t->st, t->stats, t->nch)) return r;
+    return copy_records(t->stats, host_stats, t->nch, S(stream));
 }
 
 }  // extern "C"

@@ -22,12 +22,11 @@
 // Fixed summation order (a row's result is bit-identical from run to run and whatever rows share the
 // batch): a workgroup adds the p[k] of SEG_PER_WG consecutive segments in registers, in order, and
 // stores the partial; k_scan_accum then adds a block's partials in order and the sum to A.
-#include "sdr_internal.h"
+#include "stage_host.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -290,10 +289,8 @@ int sdr_scan_create(sdr_scan** out, int device, int mode, int nsrc) {
     ScanGeom g;
     if (!scan_geom(mode, &g)) return fail(SDR_E_INVALID, "scan_create: mode %d not in 0..3", mode);
     if (nsrc < 1 || nsrc > 65535) return fail(SDR_E_INVALID, "scan_create: nsrc %d outside [1, 65535]", nsrc);
-    HIP_TRY(hipSetDevice(device));
-    sdr_scan* s = new (std::nothrow) sdr_scan;
-    if (!s) return fail(SDR_E_NOMEM, "scan_create: out of memory");
-    s->device = device;
+    sdr_scan* s = nullptr;
+    if (const int r = create_begin(&s, device, "scan_create")) return r;
     s->mode = mode;
     s->nsrc = nsrc;
     s->g = g;
@@ -326,29 +323,20 @@ int sdr_scan_create(sdr_scan** out, int device, int mode, int nsrc) {
     }
     scan_window(g.N, win.data());
     const size_t nA = (size_t)nsrc * g.N;
-    hipError_t e = hipMalloc((void**)&s->T, tab.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->win, win.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->part, nA * s->chunks * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->A, nA * sizeof(float));
+    hipError_t e = hipSuccess;
+    dev_alloc(e, &s->T, tab.size() * sizeof(float));
+    dev_alloc(e, &s->win, win.size() * sizeof(float));
+    dev_alloc(e, &s->part, nA * s->chunks * sizeof(float));
+    dev_alloc(e, &s->A, nA * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(s->T, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(s->win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(s->A, 0, nA * sizeof(float));
-    if (e != hipSuccess) {
-        sdr_scan_destroy(s);
-        return fail(e == hipErrorOutOfMemory ? SDR_E_NOMEM : SDR_E_HIP, "scan_create: %s", hipGetErrorString(e));
-    }
-    *out = s;
-    return SDR_OK;
+    return create_done(e, s, out, sdr_scan_destroy, "scan_create");
 }
 
 int sdr_scan_destroy(sdr_scan* s) {
     if (!s) return fail(SDR_E_INVALID, "scan_destroy: null scanner");
-    (void)hipSetDevice(s->device);
-    (void)hipDeviceSynchronize();   // a pending block may still use the buffers
-    for (void* p : {(void*)s->T, (void*)s->win, (void*)s->part, (void*)s->A})
-        if (p) (void)hipFree(p);
-    delete s;
-    return SDR_OK;
+    return destroy_handle(s, {s->T, s->win, s->part, s->A});
 }
 
 int sdr_scan_reset(sdr_scan* s, void* stream) {
@@ -387,8 +375,7 @@ int sdr_scan_psd(sdr_scan* s, float* psd, long long* segments, void* stream) {
     if (!s || !psd) return fail(SDR_E_INVALID, "scan_psd: null argument");
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = (size_t)s->nsrc * s->g.N;
-    HIP_TRY(hipMemcpyAsync(psd, s->A, n * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (const int r = copy_records(s->A, psd, n, S(stream))) return r;
     if (s->segments > 0) {
         const float S = (float)s->segments;
         for (size_t i = 0; i < n; i++) psd[i] = psd[i] / S;

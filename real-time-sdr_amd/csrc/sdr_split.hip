@@ -25,10 +25,9 @@
 // History: [2][nwide][2 T] bytes, the last T samples of the previous block. A block reads parity p and
 // writes parity p ^ 1 (from its input, never from the history), so no workgroup overwrites what
 // another still reads, whatever order they run in.
-#include "sdr_internal.h"
+#include "stage_host.h"
 
 #include <cmath>
-#include <new>
 #include <vector>
 
 namespace sdrk {
@@ -275,19 +274,28 @@ int sdr_split_taps(int W, int16_t* g, int max_pairs, int* n) {
     return SDR_OK;
 }
 
+// the splitter's rule for its arguments; `who` names the caller in the text. *shift <= 0 becomes W's default
+static int split_rule(const char* who, int mode, int W, int nwide, int* shift, SplitGeom* g) {
+    if (!split_geom(mode, g)) return fail(SDR_E_INVALID, "%s: mode %d not in 0..3", who, mode);
+    if (!split_w(W)) return fail(SDR_E_INVALID, "%s: W %d not 4, 8 or 10", who, W);
+    if (nwide < 1 || nwide > 4096) return fail(SDR_E_INVALID, "%s: nwide %d outside [1, 4096]", who, nwide);
+    if (*shift <= 0) *shift = split_shift_default(W);
+    if (*shift > 24) return fail(SDR_E_INVALID, "%s: shift %d outside [1, 24]", who, *shift);
+    return SDR_OK;
+}
+
+int sdr_split_check(int mode, int W, int nwide, int shift) {
+    SplitGeom g;
+    return split_rule("split_check", mode, W, nwide, &shift, &g);
+}
+
 int sdr_split_create(sdr_split** out, int device, int mode, int W, int nwide, int shift) {
     if (!out) return fail(SDR_E_INVALID, "split_create: out is NULL");
     *out = nullptr;
     SplitGeom g;
-    if (!split_geom(mode, &g)) return fail(SDR_E_INVALID, "split_create: mode %d not in 0..3", mode);
-    if (!split_w(W)) return fail(SDR_E_INVALID, "split_create: W %d not 4, 8 or 10", W);
-    if (nwide < 1 || nwide > 4096) return fail(SDR_E_INVALID, "split_create: nwide %d outside [1, 4096]", nwide);
-    if (shift <= 0) shift = split_shift_default(W);
-    if (shift > 24) return fail(SDR_E_INVALID, "split_create: shift %d outside [1, 24]", shift);
-    HIP_TRY(hipSetDevice(device));
-    sdr_split* s = new (std::nothrow) sdr_split;
-    if (!s) return fail(SDR_E_NOMEM, "split_create: out of memory");
-    s->device = device;
+    if (const int r = split_rule("split_create", mode, W, nwide, &shift, &g)) return r;
+    sdr_split* s = nullptr;
+    if (const int r = create_begin(&s, device, "split_create")) return r;
     s->mode = mode;
     s->W = W;
     s->nwide = nwide;
@@ -295,28 +303,19 @@ int sdr_split_create(sdr_split** out, int device, int mode, int W, int nwide, in
     s->g = g;
     const std::vector<int8_t> f = split_fragments(W);
     const size_t nh = (size_t)2 * nwide * 32 * W, nc = (size_t)nwide * (2 * W - 1) * CLIP_SLOTS;
-    hipError_t e = hipMalloc((void**)&s->hist, nh);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->bfrag, f.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&s->clips, nc * sizeof(unsigned long long));
+    hipError_t e = hipSuccess;
+    dev_alloc(e, &s->hist, nh);
+    dev_alloc(e, &s->bfrag, f.size());
+    dev_alloc(e, &s->clips, nc * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemcpy(s->bfrag, f.data(), f.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(s->hist, 0, nh);
     if (e == hipSuccess) e = hipMemset(s->clips, 0, nc * sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        sdr_split_destroy(s);
-        return fail(e == hipErrorOutOfMemory ? SDR_E_NOMEM : SDR_E_HIP, "split_create: %s", hipGetErrorString(e));
-    }
-    *out = s;
-    return SDR_OK;
+    return create_done(e, s, out, sdr_split_destroy, "split_create");
 }
 
 int sdr_split_destroy(sdr_split* s) {
     if (!s) return fail(SDR_E_INVALID, "split_destroy: null splitter");
-    (void)hipSetDevice(s->device);
-    (void)hipDeviceSynchronize();   // a pending block may still use the buffers
-    for (void* p : {(void*)s->hist, (void*)s->bfrag, (void*)s->clips})
-        if (p) (void)hipFree(p);
-    delete s;
-    return SDR_OK;
+    return destroy_handle(s, {s->hist, s->bfrag, s->clips});
 }
 
 int sdr_split_reset(sdr_split* s, void* stream) {
@@ -363,9 +362,7 @@ int sdr_split_clips(sdr_split* s, long long* clips, void* stream) {
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = (size_t)s->nwide * (2 * s->W - 1);
     std::vector<unsigned long long> part(n * CLIP_SLOTS);
-    HIP_TRY(hipMemcpyAsync(part.data(), s->clips, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                           (hipStream_t)stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (const int r = copy_records(s->clips, part.data(), part.size(), S(stream))) return r;
     for (size_t i = 0; i < n; i++) {
         unsigned long long sum = 0;
         for (int k = 0; k < CLIP_SLOTS; k++) sum += part[i * CLIP_SLOTS + k];

@@ -39,7 +39,8 @@
 // and its next parity reuse on s_fe after its post on s_post, so no wait on one stream can sit in
 // front of the work it waits for on the other.
 //
-// A run is described once (RunSpec), judged once, before any device call (validate), and owns what it
+// A run is described once (RunSpec), judged once, before any device call (validate: the stages' own bounds
+// through the library's sdr_*_check functions, the engine's rules spelt out), and owns what it
 // makes: every event, buffer, stream, context and file is released by the destructor of the object
 // that holds it, in the reverse order of declaration.
 //
@@ -108,48 +109,39 @@ struct RunSpec {
     const sdr_rds_carrier_opts* carrier = nullptr;   // the derotated rows for the tracker (sdr_multi_run_rds_carrier)
 };
 
-// Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused.
+// Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused. A stage's
+// own bounds are the library's (its _check function, which its create calls too); what is spelt out here is what
+// only the engine knows.
 bool validate(const RunSpec& r) {
     const sdr_multi_opts* o = r.o;
     if (!o || (r.blend && (!r.meter || !r.audio))) return false;
     if ((o->flags & SDR_FLAG_FAST_FRONTEND) && (o->flags & SDR_FLAG_PHASE_DEMOD)) return false;   // sdr_ctx_create's rule
     if (o->flags & SDR_FLAG_RDS_QUAD) return false;   // the engine sets it itself, on the RDS thread's context (carrier)
-    if (r.audio) {   // what sdr_audio_create would refuse
-        float a = 0.0f, b = 0.0f;
-        if (sdr_audio_coeffs(o->mode, r.audio->tau_us, &a, &b) != SDR_OK || !(r.audio->blend_hi > r.audio->blend_lo)) return false;
-    }
+    if (r.audio && sdr_audio_opts_check(o->mode, r.audio) != SDR_OK) return false;
     if (o->nch <= 0 || (!o->in_path && (!o->d_iq || o->nblocks <= 0))) return false;
-    if (const sdr_multi_rds* d = r.rds)   // what sdr_rds_dec_create would refuse, and a mode without an RDS bit clock
-        if (d->max_burst < 0 || d->max_burst > 5 || d->loss_blocks < 1 || d->loss_blocks > 64 || !sdr_rds_mode_ok(o->mode))
-            return false;
-    if (r.rds_clock != SDR_MULTI_RDS_CLOCK_REF) {   // the tracker feeds the decoder only; what sdr_rds_track_create would refuse
-        const sdr_rds_track_opts* t = r.track;
-        if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds || !t) return false;
-        if (t->qshift < 0 || t->qshift > 15 || t->acquire_bits < 1 || t->acquire_bits > 64 || t->half_bits < SDR_RDS_TRACK_T ||
-            t->half_bits > 64 || t->half_bits % SDR_RDS_TRACK_T)
-            return false;
+    if (const sdr_multi_rds* d = r.rds) {   // the decoder's record, and a mode with an RDS bit clock
+        const sdr_rds_opts ro{d->max_burst, d->loss_blocks};
+        if (sdr_rds_opts_check(&ro) != SDR_OK || !sdr_rds_mode_ok(o->mode)) return false;
     }
-    if (const sdr_rds_soft_opts* q = r.soft) {   // only the tracker has reliabilities; what sdr_rds_dec_create_soft would refuse
+    if (r.rds_clock != SDR_MULTI_RDS_CLOCK_REF) {   // the tracker feeds the decoder only
+        if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds || !r.track) return false;
+        if (sdr_rds_track_opts_check(o->mode, r.track) != SDR_OK) return false;
+    }
+    if (r.soft) {   // only the tracker has reliabilities
         if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds) return false;
-        if (q->max_burst < 0 || q->max_burst > 5 || q->loss_blocks < 1 || q->loss_blocks > 64 || q->soft_bits < 0 || q->soft_bits > 6)
-            return false;
+        if (sdr_rds_soft_opts_check(r.soft) != SDR_OK) return false;
     }
-    if (const sdr_rds_carrier_opts* q = r.carrier) {   // the tracker reads its rows; what sdr_rds_carrier_create would refuse
+    if (r.carrier) {   // the tracker reads its rows
         if (r.rds_clock != SDR_MULTI_RDS_CLOCK_TRACK || !r.rds) return false;
-        if (q->qshift < 0 || q->qshift > 15 || q->avg_shift < 0 || q->avg_shift > 6) return false;
+        if (sdr_rds_carrier_opts_check(o->mode, r.carrier) != SDR_OK) return false;
     }
-    if (const sdr_multi_tuning* t = r.tune) {   // the tuning's bounds (sdr_tuner_set's)
-        int N = 0;
-        if (sdr_tuner_table(o->mode, nullptr, 0, &N) != SDR_OK) return false;
-        if (t->nsrc < 1 || t->nsrc > o->nch || !t->src || !t->khz) return false;
-        for (int c = 0; c < o->nch; c++)
-            if (t->src[c] < 0 || t->src[c] >= t->nsrc || 2 * (long long)t->khz[c] <= -(long long)N || 2 * (long long)t->khz[c] > N)
-                return false;
-    }
+    // a tuned run has capture rows: nsrc = 0 is how sdr_tuner_set takes a tuning away
+    if (r.tune && (r.tune->nsrc == 0 || sdr_tuner_check(o->mode, o->nch, r.tune->nsrc, r.tune->src, r.tune->khz) != SDR_OK))
+        return false;
     int in_iq = 0;   // samples of an input row; left 0 for a mode the scanner does not know: sdr_ctx_create ends that run
     if (const sdr_multi_wide* w = r.wide) {   // a wide run is always tuned, on rows the splitter makes
         int R = 0;
-        if (!r.tune || w->nwide < 1 || w->nwide > 4096 || w->shift > 24 ||
+        if (!r.tune || sdr_split_check(o->mode, w->W, w->nwide, w->shift) != SDR_OK ||
             sdr_split_geometry(o->mode, w->W, &R, nullptr, &in_iq, nullptr, nullptr) != SDR_OK || r.tune->nsrc > w->nwide * R)
             return false;
         if (!o->in_path && ((o->row_stride & 3) || (reinterpret_cast<uintptr_t>(o->d_iq) & 3) || (o->block_stride & 3))) return false;
