@@ -317,6 +317,53 @@ int sdr_split_block(sdr_split *s, const int8_t *wide, size_t wide_stride, uint8_
 /* clips: host [nwide * R], accumulated since the last reset; synchronises `stream` */
 int sdr_split_clips(sdr_split *s, long long *clips, void *stream);
 
+/* ---- 16-bit wideband splitter (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
+ * the splitter above for the sc16 stream of a USRP, bladeRF, LimeSDR, Pluto or SDRplay, with a shift per stream
+ * and row and a peak reading per row, so that a row that holds only a weak station gets its own gain. W, R, T,
+ * the taps (exactly sdr_split_taps(W): no new table), the rows, the history and the sign flip are as above.
+ * All integer, so every correct implementation gives the same bytes, clip counts and peaks.
+ *   input    [nwide][2 W block_iq] little-endian int16, I then Q (4 W block_iq bytes per stream and block);
+ *            zeros before the first block and after a reset
+ *   sums     acc_re, acc_im: the formulas above on the 16-bit samples, in 64-bit integers, negated when k t is
+ *            odd. With the shipped taps max_col sum |e| is 75012, 148820, 185844 for W = 4, 8, 10, so |acc| is
+ *            at most 2.46e9, 4.88e9, 6.09e9: under 2^33 and over 2^31 for every W
+ *   output   v = 128 + ((acc + (1 << (s - 1))) >> s)          (arithmetic shift on int64)
+ *            s = shift[stream][r] in 1..33, a shift per stream and row; default 22, 23, 24 for W = 4, 8, 10
+ *            (the s8 defaults + 8: the same gain relative to full scale)
+ *            out = clamp(v, 0, 255); each component with v < 0 or v > 255 adds 1 to clips[stream][r]
+ *   peaks    peaks[stream][r] = max of max(|acc_re|, |acc_im|) over every output sample of the row since the
+ *            last reset or clearing read; it does not depend on the shifts
+ *   gain     sdr_split16_shift_for(peak, target, W), target in 1..127 (90 is the usual one): with
+ *            rnd(p, s) = (p + (1 << (s - 1))) >> s, the smallest s in 1..33 with rnd(peak, s) <= target; W's
+ *            default for peak == 0. A block whose peaks chose the shifts clips nothing when split with them,
+ *            and every row given s > 1 then has an output excursion max |out - 128| >= target / 2 (floor).
+ *   An s8 capture widened as 256 x and split with shift s + 8 on every row gives the rows and clips of sdr_split
+ *   at shift s ((256 a + 2^(s+7)) >> (s + 8) == (a + 2^(s-1)) >> s); so does the same capture sign-extended, at
+ *   shift s (s in 1..24).
+ *
+ * Geometry: sdr_split_geometry (a wide block is 2 wide_iq int16 values). shift <= 0 takes the default.
+ * SDR_E_INVALID, with nothing enqueued and nothing changed, for a bad mode, W, nwide (1..4096) or shift, a shifts
+ * table with a value outside 1..33, NULL pointers, wide_stride (in bytes) < 4 W block_iq or no multiple of 4, wide
+ * not 4-byte aligned, or a rows / row_stride that sdr_split_block would refuse. */
+typedef struct sdr_split16 sdr_split16;
+int sdr_split16_create(sdr_split16 **out, int device, int mode, int W, int nwide, int shift);
+/* host only, no GPU: SDR_OK when sdr_split16_create takes these arguments */
+int sdr_split16_check(int mode, int W, int nwide, int shift);
+int sdr_split16_destroy(sdr_split16 *s);
+/* history, clip counters and peaks back to 0; the shifts stay as they are */
+int sdr_split16_reset(sdr_split16 *s, void *stream);
+/* shifts: host [nwide * R], all judged first. Ordered on `stream` like a block call: it holds for the block
+ * calls enqueued after it, no sync (the table lives in device memory; the caller's array may go at once) */
+int sdr_split16_set_shifts(sdr_split16 *s, const int *shifts, void *stream);
+/* one block of every stream: one launch on `stream`, no sync */
+int sdr_split16_block(sdr_split16 *s, const int16_t *wide, size_t wide_stride, uint8_t *rows, size_t row_stride,
+                      void *stream);
+/* clips, peaks: host [nwide * R], since the last reset (peaks: or clearing read, clear != 0); synchronise `stream` */
+int sdr_split16_clips(sdr_split16 *s, long long *clips, void *stream);
+int sdr_split16_peaks(sdr_split16 *s, long long *peaks, int clear, void *stream);
+/* host only, no GPU: the gain rule above; SDR_E_INVALID (negative) for a bad target, W or a negative peak */
+int sdr_split16_shift_for(long long peak, int target, int W);
+
 /* ---- reception meter (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
  * per channel and block, what a receiver's stereo lamp and tuning indicator show, reduced on the GPU
  * from rows the pipeline already keeps. n = block_if, x = the block's fm_demod row, x[-100..-1] the

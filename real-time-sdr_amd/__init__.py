@@ -242,6 +242,15 @@ def lib() -> C.CDLL:
         "sdr_split_reset": ([vp, vp], i32),
         "sdr_split_block": ([vp, vp, sz, vp, sz, vp], i32),
         "sdr_split_clips": ([vp, vp, vp], i32),
+        "sdr_split16_create": ([C.POINTER(vp), i32, i32, i32, i32, i32], i32),
+        "sdr_split16_check": ([i32, i32, i32, i32], i32),
+        "sdr_split16_destroy": ([vp], i32),
+        "sdr_split16_reset": ([vp, vp], i32),
+        "sdr_split16_set_shifts": ([vp, vp, vp], i32),
+        "sdr_split16_block": ([vp, vp, sz, vp, sz, vp], i32),
+        "sdr_split16_clips": ([vp, vp, vp], i32),
+        "sdr_split16_peaks": ([vp, vp, i32, vp], i32),
+        "sdr_split16_shift_for": ([C.c_longlong, i32, i32], i32),
         "sdr_meter_taps": ([i32, vp, i32, C.POINTER(i32)], i32),
         "sdr_meter_opts_default": ([C.POINTER(MeterOpts)], None),
         "sdr_meter_status": ([i32, C.POINTER(MeterRow), C.POINTER(MeterOpts), C.POINTER(MeterState)], i32),
@@ -567,6 +576,82 @@ class Splitter(_Handle):
         c = np.zeros((self.nwide, self.rows), np.int64)
         check(lib().sdr_split_clips(self._h, c.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_split_clips")
         return c
+
+
+def split16_shift_for(peak: int, target: int = 90, *, W: int) -> int:
+    """The 16-bit splitter's gain rule (host only): the smallest shift in 1..33 at which `peak` rounds to at most
+    `target` (1..127); W's default shift for a peak of 0."""
+    s = lib().sdr_split16_shift_for(int(peak), int(target), int(W))
+    if s < 1:
+        check(s, "sdr_split16_shift_for")
+    return s
+
+
+class Splitter16(_Handle):
+    """The Splitter for wide int16 I/Q captures (sdr_split16_*): a shift per stream and row (set_shifts) and a
+    peak reading per row (peaks), so that each row can have its own gain. Its own handle: any stream."""
+
+    _destroy, _reset = "sdr_split16_destroy", "sdr_split16_reset"
+
+    def __init__(self, W: int, nwide: int, mode: int = 0, device: int = 0, shift=None):
+        import numpy as np
+        h = C.c_void_p()
+        check(lib().sdr_split16_create(C.byref(h), device, mode, W, nwide, 0 if shift is None else int(shift)),
+              "sdr_split16_create")
+        self._h = h
+        self.W, self.nwide, self.mode, self.device = W, nwide, mode, device
+        self.rows, self.taps, self.wide_iq, self.half_khz, d = split_geometry(mode, W)
+        self.shift_default = d + 8
+        self.block_iq = self.wide_iq // W
+        self._shifts = np.full((nwide, self.rows), self.shift_default if shift is None or shift <= 0 else int(shift),
+                               np.int32)
+
+    @property
+    def shifts(self):
+        """numpy int32 [nwide][R]: the table of the last set_shifts (or the shift of the constructor); a copy."""
+        return self._shifts.copy()
+
+    def set_shifts(self, shifts, stream=None):
+        """shifts: ints [nwide][R] (or nwide * R), each in 1..33. Holds for the block calls enqueued after it on
+        the stream; no sync. A refused table changes nothing."""
+        import numpy as np
+        t = np.ascontiguousarray(np.asarray(shifts), np.int32)
+        if t.size != self.nwide * self.rows:
+            raise SdrError(f"Splitter16.set_shifts: expected {self.nwide} x {self.rows} shifts", -1)
+        check(lib().sdr_split16_set_shifts(self._h, t.ctypes.data_as(C.c_void_p), _stream(stream)),
+              "sdr_split16_set_shifts")
+        self._shifts = t.reshape(self.nwide, self.rows).copy()
+
+    def block(self, wide, out=None, stream=None):
+        """wide: int16 [nwide][2*W*block_iq] (device). Returns the uint8 rows [nwide*R][2*block_iq] (out, or
+        a new tensor); enqueues, no sync."""
+        import torch
+        if wide.dim() != 2 or wide.shape[0] != self.nwide or wide.dtype != torch.int16:
+            raise SdrError(f"Splitter16.block: expected int16 [{self.nwide}][2*W*block_iq] streams", -1)
+        if out is None:
+            out = torch.empty((self.nwide * self.rows, 2 * self.block_iq), dtype=torch.uint8, device=wide.device)
+        elif out.dim() != 2 or out.shape[0] != self.nwide * self.rows or out.dtype != torch.uint8:
+            raise SdrError(f"Splitter16.block: expected uint8 [{self.nwide * self.rows}][2*block_iq] rows", -1)
+        ws = _row_stride(wide) if wide.shape[0] > 1 else int(wide.shape[1])
+        check(lib().sdr_split16_block(self._h, _ptr(wide), 2 * ws, _ptr(out), _row_stride(out), _stream(stream)),
+              "sdr_split16_block")
+        return out
+
+    def clips(self, stream=None):
+        """numpy int64 [nwide][R]: clipped output components since the last reset; synchronises the stream."""
+        import numpy as np
+        c = np.zeros((self.nwide, self.rows), np.int64)
+        check(lib().sdr_split16_clips(self._h, c.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_split16_clips")
+        return c
+
+    def peaks(self, clear: bool = False, stream=None):
+        """numpy int64 [nwide][R]: the largest |acc_re| or |acc_im| of each row since the last reset or clearing
+        read (clear=True makes this one); independent of the shifts; synchronises the stream."""
+        import numpy as np
+        p = np.zeros((self.nwide, self.rows), np.int64)
+        check(lib().sdr_split16_peaks(self._h, p.ctypes.data_as(C.c_void_p), 1 if clear else 0, _stream(stream)),
+              "sdr_split16_peaks")
+        return p
 
 
 # ------------------------------------------------------------------ reception meter (include/sdr_amd.h, sdr_meter_*)

@@ -33,6 +33,11 @@
 // block; with --scan NWIDE wide streams are scanned and PREFIX.stations names the capture rows, so
 // `sdr_multi <n> --wide W --tune PREFIX.stations` receives what `sdr_multi NWIDE --wide W --scan` found.
 // The summary line counts the wide bytes read; clip counts go to stderr when any are non-zero.
+// --wide-format s16 (with --wide; s8 is the default): the wide input is little-endian int16 I/Q, rows of
+// 4*W*block_iq bytes (include/sdr_multi_wide16.h), cut by the 16-bit splitter. --shift S is then 1-33 (default 22,
+// 23, 24) and holds for every row; --wide-gain auto[:TARGET] instead takes a shift per row from block 0's peaks
+// (target 1-127, default 90). A receiver run also writes PREFIX.wide, one line "stream row shift peak clips" per
+// capture row.
 // --demod phase: the phase discriminator (SDR_FLAG_PHASE_DEMOD, include/sdr_amd.h) instead of the
 // reference's (--demod ref, the default): the audio of a loud station no longer folds, and with --meter every
 // PREFIX.status line also ends with the run's peak deviation and mean offset in kHz. Not with --fast.
@@ -67,6 +72,7 @@
 #include "sdr_multi_rds.h"
 #include "sdr_multi_tuned.h"
 #include "sdr_multi_wide.h"
+#include "sdr_multi_wide16.h"
 #include "sdr_scan_run.h"
 #include "sdr_wide_scan.h"
 
@@ -93,7 +99,10 @@ namespace {
                          "            carrier phase found in them, for the tracker (ref, default: rds_clean alone); needs --rds-clock track\n"
                          "  --scan: write the stations of NROWS capture rows to PREFIX.stations (the --tune format)\n"
                          "  --wide W: the input is wide int8 I/Q at W (4, 8, 10) times rf_Fs, rows of 2*W*block_iq bytes, each\n"
-                         "            split into 2W-1 capture rows (--shift S: output shift 1-24); needs --tune or --scan\n");
+                         "            split into 2W-1 capture rows (--shift S: output shift 1-24); needs --tune or --scan\n"
+                         "  --wide-format s8|s16: with --wide; s16: int16 I/Q, rows of 4*W*block_iq bytes, --shift 1-33, or\n"
+                         "            --wide-gain auto[:TARGET] (a shift per row from block 0's peaks, target 1-127, default 90);\n"
+                         "            a receiver run also writes PREFIX.wide (stream, row, shift, peak, clips per capture row)\n");
     std::exit(1);
 }
 }  // namespace
@@ -111,6 +120,8 @@ int main(int argc, char** argv) {
     sdr_rds_opts ro{};
     sdr_rds_opts_default(&ro);
     int wide_w = 0, wide_shift = 0;
+    bool wide_format_set = false, wide_gain_set = false;
+    sdr_wide_fmt wf{};
     sdr_audio_opts ao{};
     sdr_audio_opts_default(&ao);
     sdr_scan_run_opts so{};
@@ -129,7 +140,29 @@ int main(int argc, char** argv) {
         }
         else if (a == "--shift" && i + 1 < argc) {
             wide_shift = std::atoi(argv[++i]);
-            if (wide_shift < 1 || wide_shift > 24) usage();
+            if (wide_shift < 1 || wide_shift > 33) usage();   // (above 24: with --wide-format s16 only, below)
+        }
+        else if (a == "--wide-format" && i + 1 < argc) {
+            const std::string f = argv[++i];
+            if (f == "s16") wf.format = SDR_WIDE_S16;
+            else if (f == "s8") wf.format = SDR_WIDE_S8;
+            else usage();
+            wide_format_set = true;
+        }
+        else if (a == "--wide-gain" && i + 1 < argc) {
+            const std::string g = argv[++i];
+            if (g == "fixed") wf.gain = SDR_WIDE_GAIN_FIXED;
+            else if (g.rfind("auto", 0) == 0 && (g.size() == 4 || g[4] == ':')) {
+                wf.gain = SDR_WIDE_GAIN_AUTO;
+                if (g.size() > 4) {
+                    char* end = nullptr;
+                    const long t = std::strtol(g.c_str() + 5, &end, 10);
+                    if (g.size() == 5 || *end || t < 1 || t > 127) usage();
+                    wf.target = (int)t;
+                }
+            }
+            else usage();
+            wide_gain_set = true;
         }
         else if (a == "--meter") meter = true;
         else if (a == "--blend") blend = finish = true;
@@ -186,6 +219,9 @@ int main(int argc, char** argv) {
     if (rds_quad && (!rds_decode || rds_clock != SDR_MULTI_RDS_CLOCK_TRACK)) usage();   // the tracker reads the rotated rows
     if (rds_decode && (scan || !sdr_rds_mode_ok(o.mode))) usage();   // a scan demodulates nothing; modes 1-3 have no RDS bit clock
     if (wide_shift && !wide_w) usage();
+    if ((wide_format_set || wide_gain_set) && !wide_w) usage();
+    if (wf.format != SDR_WIDE_S16 && (wide_gain_set || wide_shift > 24)) usage();   // the s8 splitter has one shift, 1-24
+    if (wf.gain == SDR_WIDE_GAIN_AUTO && wide_shift) usage();                       // one or the other
     if (wide_w && !scan && tune_path.empty()) usage();        // a wide run is always tuned
     if (scan && wide_w) {
         if (!tune_path.empty() || meter || finish) usage();
@@ -201,7 +237,7 @@ int main(int argc, char** argv) {
         wo.max_blocks = so.max_blocks;
         wo.pick = so.pick;
         sdr_wide_scan_stats ws{};
-        const int rc = sdr_wide_scan_run(&wo, &ws);
+        const int rc = wf.format == SDR_WIDE_S16 ? sdr_wide_scan_run_fmt(&wo, &wf, &ws) : sdr_wide_scan_run(&wo, &ws);
         if (rc != SDR_OK) {
             std::fprintf(stderr, "sdr_multi: %d %s\n", rc, ws.error);
             return 1;
@@ -255,13 +291,20 @@ int main(int argc, char** argv) {
     }
     const int wide_r = 2 * wide_w - 1;
     sdr_multi_wide wd{};
-    std::vector<long long> clips;
+    std::vector<long long> clips, wide_peaks;
+    std::vector<int> wide_shifts;
     if (wide_w) {
         wd.W = wide_w;
         wd.nwide = (tune.nsrc + wide_r - 1) / wide_r;
         wd.shift = wide_shift;
         clips.assign((size_t)(wd.nwide > 0 ? wd.nwide : 1) * wide_r, 0);
         wd.clips = clips.data();
+        if (wf.format == SDR_WIDE_S16) {
+            wide_shifts.assign(clips.size(), 0);
+            wide_peaks.assign(clips.size(), 0);
+            wf.shifts_out = wide_shifts.data();
+            wf.peaks_out = wide_peaks.data();
+        }
     }
     const int rows = wide_w ? wd.nwide : tune_path.empty() ? o.nch : tune.nsrc;
     sdr_meter_opts mo{};
@@ -271,7 +314,11 @@ int main(int argc, char** argv) {
     const sdr_rds_soft_opts sq{ro.max_burst, ro.loss_blocks, rds_soft};
     sdr_rds_carrier_opts cq{};
     sdr_rds_carrier_opts_default(&cq);
-    const int rc = rds_decode ? sdr_multi_run_rds_carrier(&o, wide_w ? &wd : nullptr, tp, meter ? &mo : nullptr,
+    const bool s16 = wide_w && wf.format == SDR_WIDE_S16;
+    const int rc = s16 ? sdr_multi_run_wide_fmt(&o, &wd, tp, meter ? &mo : nullptr, finish ? &ao : nullptr, blend ? 1 : 0,
+                                                rds_decode ? &rd : nullptr, rds_decode ? rds_clock : SDR_MULTI_RDS_CLOCK_REF, nullptr,
+                                                rds_soft ? &sq : nullptr, rds_quad ? &cq : nullptr, &wf, &st)
+                   : rds_decode ? sdr_multi_run_rds_carrier(&o, wide_w ? &wd : nullptr, tp, meter ? &mo : nullptr,
                                                           finish ? &ao : nullptr, blend ? 1 : 0, &rd, rds_clock, nullptr,
                                                           rds_soft ? &sq : nullptr, rds_quad ? &cq : nullptr, &st)
                    : wide_w ? sdr_multi_run_wide(&o, &wd, tp, meter ? &mo : nullptr, finish ? &ao : nullptr, blend ? 1 : 0, &st)
@@ -283,6 +330,17 @@ int main(int argc, char** argv) {
                      tune_path.empty() ? "" : " (--tune: 0 <= src < NCH rows, -N/2 < khz <= N/2, N = rf_Fs / 1000)");
         return 1;
     }
+    if (s16) {   // the gain each capture row had and what it did with it
+        const std::string path = out + ".wide";
+        FILE* f = std::fopen(path.c_str(), "w");
+        if (!f) {
+            std::fprintf(stderr, "sdr_multi: cannot write %s\n", path.c_str());
+            return 1;
+        }
+        for (size_t i = 0; i < clips.size(); i++)
+            std::fprintf(f, "%zu %zu %d %lld %lld\n", i / (size_t)wide_r, i % (size_t)wide_r, wide_shifts[i], wide_peaks[i], clips[i]);
+        std::fclose(f);
+    }
     for (size_t i = 0; i < clips.size(); i++)
         if (clips[i])
             std::fprintf(stderr, "sdr_multi: splitter: wide stream %zu row %zu: %lld output components clipped\n",
@@ -293,7 +351,7 @@ int main(int argc, char** argv) {
     sdr_ctx_destroy(probe);
     const double samples = (double)st.blocks * o.nch * info.block_iq;
     const double signal_s = (double)st.blocks * info.block_iq / (double)info.rf_Fs;
-    const double in_gb = (double)st.blocks * rows * 2.0 * info.block_iq * (wide_w ? wide_w : 1) / 1e9;   // (a wide run: the wide bytes)
+    const double in_gb = (double)st.blocks * rows * (s16 ? 4.0 : 2.0) * info.block_iq * (wide_w ? wide_w : 1) / 1e9;   // (a wide run: the wide bytes)
     char after0[128] = "after block 0 n/a (fewer than 2 blocks)";
     if (st.blocks >= 2 && st.steady_seconds > 0)
         std::snprintf(after0, sizeof(after0), "after block 0 %.1f MS/s (%.1fx real time)",

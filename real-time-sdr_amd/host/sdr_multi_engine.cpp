@@ -86,6 +86,8 @@
 #include "sdr_multi_rds.h"
 #include "sdr_multi_tuned.h"
 #include "sdr_multi_wide.h"
+#include "sdr_multi_wide16.h"
+#include "wide16.h"
 
 using sdrhost::check_hip;
 using sdrhost::check_sdr;
@@ -107,6 +109,7 @@ struct RunSpec {
     const sdr_rds_track_opts* track = nullptr;   // the tracker's options, with SDR_MULTI_RDS_CLOCK_TRACK
     const sdr_rds_soft_opts* soft = nullptr;  // soft decisions on the tracker's clock (sdr_multi_run_rds_soft)
     const sdr_rds_carrier_opts* carrier = nullptr;   // the derotated rows for the tracker (sdr_multi_run_rds_carrier)
+    const sdr_wide_fmt* fmt = nullptr;        // int16 wide captures and their gain (sdr_multi_run_wide_fmt)
 };
 
 // Everything SDR_E_INVALID stands for, host arithmetic only: nothing exists yet when a run is refused. A stage's
@@ -141,11 +144,15 @@ bool validate(const RunSpec& r) {
     int in_iq = 0;   // samples of an input row; left 0 for a mode the scanner does not know: sdr_ctx_create ends that run
     if (const sdr_multi_wide* w = r.wide) {   // a wide run is always tuned, on rows the splitter makes
         int R = 0;
-        if (!r.tune || sdr_split_check(o->mode, w->W, w->nwide, w->shift) != SDR_OK ||
+        const bool s16 = sdrhost::wide16(r.fmt);
+        if (s16 && sdrhost::wide_fmt_refusal(r.fmt, o->mode, w->W, w->nwide, w->shift)) return false;
+        if (!r.tune || (!s16 && sdr_split_check(o->mode, w->W, w->nwide, w->shift) != SDR_OK) ||
             sdr_split_geometry(o->mode, w->W, &R, nullptr, &in_iq, nullptr, nullptr) != SDR_OK || r.tune->nsrc > w->nwide * R)
             return false;
+        if (s16) in_iq *= 2;   // (an int16 row is twice the bytes)
         if (!o->in_path && ((o->row_stride & 3) || (reinterpret_cast<uintptr_t>(o->d_iq) & 3) || (o->block_stride & 3))) return false;
     } else {
+        if (sdrhost::wide16(r.fmt)) return false;   // int16 rows are wide rows
         (void)sdr_scan_geometry(o->mode, nullptr, nullptr, &in_iq);   // block_iq, the contexts' (sdr_ctx_info)
     }
     return o->in_path || o->row_stride >= 2 * (size_t)in_iq;
@@ -576,15 +583,43 @@ struct AudioFin {
 };
 
 // A wide run's splitter and its geometry: nwide * (2 W - 1) capture rows per block from rows of 2 * wide_iq bytes
+// (int8 streams, s) or 4 * wide_iq bytes (int16 streams, s16: a shift per row, fixed or from block 0's peaks)
 struct Splitter {
     sdr_split* s = nullptr;
-    int rows = 0, wide_iq = 0;
-    Splitter(const sdr_multi_opts& o, const sdr_multi_wide& w) {
+    sdr_split16* s16 = nullptr;
+    int rows = 0, wide_iq = 0, W = 0;
+    size_t in_row = 0;                   // bytes of a wide stream's block
+    int auto_target = -1;                // >= 0: the shifts come from block 0 (0: the default target)
+    std::vector<int> shifts;             // s16: the table in use
+    Splitter(const sdr_multi_opts& o, const sdr_multi_wide& w, const sdr_wide_fmt* f) : W(w.W) {
         check_sdr(sdr_split_geometry(o.mode, w.W, &rows, nullptr, &wide_iq, nullptr, nullptr), "sdr_split_geometry");
         rows *= w.nwide;
-        check_sdr(sdr_split_create(&s, o.device, o.mode, w.W, w.nwide, w.shift), "sdr_split_create");
+        in_row = (sdrhost::wide16(f) ? 4 : 2) * (size_t)wide_iq;
+        if (!sdrhost::wide16(f)) {
+            check_sdr(sdr_split_create(&s, o.device, o.mode, w.W, w.nwide, w.shift), "sdr_split_create");
+            return;
+        }
+        check_sdr(sdr_split16_create(&s16, o.device, o.mode, w.W, w.nwide, w.shift), "sdr_split16_create");
+        shifts.assign((size_t)rows, w.shift > 0 ? w.shift : sdr_split16_shift_for(0, 90, w.W));
+        if (f->shifts) {
+            shifts.assign(f->shifts, f->shifts + rows);
+            check_sdr(sdr_split16_set_shifts(s16, shifts.data(), nullptr), "sdr_split16_set_shifts");
+        }
+        if (f->gain == SDR_WIDE_GAIN_AUTO) auto_target = f->target;
     }
-    ~Splitter() { (void)sdr_split_destroy(s); }
+    // block 0 of an auto gain run, in front of its block call: the shifts from its peaks (scratch: rows nobody reads)
+    void gain_from(const uint8_t* src, size_t stride, uint8_t* scratch, size_t row, hipStream_t st) {
+        check_sdr(sdrhost::wide16_auto_gain(s16, W, auto_target, reinterpret_cast<const int16_t*>(src), stride, scratch, row,
+                                            st, &shifts), "the wide run's auto gain");
+    }
+    void block(const uint8_t* src, size_t stride, uint8_t* out, size_t row, hipStream_t st) {
+        if (s16) check_sdr(sdr_split16_block(s16, reinterpret_cast<const int16_t*>(src), stride, out, row, st), "sdr_split16_block");
+        else check_sdr(sdr_split_block(s, reinterpret_cast<const int8_t*>(src), stride, out, row, st), "sdr_split_block");
+    }
+    ~Splitter() {
+        if (s) (void)sdr_split_destroy(s);
+        if (s16) (void)sdr_split16_destroy(s16);
+    }
 };
 
 // a recycled device batch of fm_demod [nch][block_if] and its events (include/dropin/fm_batch.h)
@@ -780,8 +815,8 @@ void rf_thread(Shared* sh) {
         if (sh->split) {
             const int k = (int)(b & 1);
             if (b >= 2) check_hip(hipStreamWaitEvent(sf, rows_done[k], 0), "hipStreamWaitEvent");
-            check_sdr(sdr_split_block(sh->split->s, reinterpret_cast<const int8_t*>(src), stride, d_rows[k].p, row, sf),
-                      "sdr_split_block");
+            if (b == 0 && sh->split->auto_target >= 0) sh->split->gain_from(src, stride, d_rows[1].p, row, sf);
+            sh->split->block(src, stride, d_rows[k].p, row, sf);
             check_sdr(sdr_frontend_tuned(ctx, d_rows[k].p, row, sf), "sdr_frontend_tuned");
             check_hip(hipEventRecord(rows_done[k], sf), "hipEventRecord");
         } else if (sh->tuned) check_sdr(sdr_frontend_tuned(ctx, src, stride, sf), "sdr_frontend_tuned");
@@ -1109,8 +1144,8 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
         check_sdr(spec.tune ? sdr_tuner_set(c, spec.tune->nsrc, spec.tune->src, spec.tune->khz, nullptr)
                             : sdr_tuner_set(c, 0, nullptr, nullptr, nullptr), "sdr_tuner_set");
     check_sdr(sdr_ctx_info(sh.ctx[0], &sh.info), "sdr_ctx_info");
-    if (spec.wide) sh.split.emplace(o, *spec.wide);
-    sh.in_row = spec.wide ? 2 * (size_t)sh.split->wide_iq : 2 * (size_t)sh.info.block_iq;
+    if (spec.wide) sh.split.emplace(o, *spec.wide, spec.fmt);
+    sh.in_row = spec.wide ? sh.split->in_row : 2 * (size_t)sh.info.block_iq;
     sh.nblocks_known = o.in_path ? regular_file_blocks(o.in_path, sh.in_row * (size_t)sh.rows) : o.nblocks;
     // streams: the PLLs on [0, pll_cus) (halves), everything else on the rest
     const int half = o.pll_cus / 2;
@@ -1197,7 +1232,13 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     // The one order that matters at the end: the device is idle before sh releases anything, and the
     // splitter's clip counters are read while the splitter exists.
     check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    if (sh.split && spec.wide->clips) check_sdr(sdr_split_clips(sh.split->s, spec.wide->clips, nullptr), "sdr_split_clips");
+    if (sh.split && sh.split->s && spec.wide->clips)
+        check_sdr(sdr_split_clips(sh.split->s, spec.wide->clips, nullptr), "sdr_split_clips");
+    if (sh.split && sh.split->s16) {
+        if (spec.wide->clips) check_sdr(sdr_split16_clips(sh.split->s16, spec.wide->clips, nullptr), "sdr_split16_clips");
+        if (spec.fmt->peaks_out) check_sdr(sdr_split16_peaks(sh.split->s16, spec.fmt->peaks_out, 0, nullptr), "sdr_split16_peaks");
+        if (spec.fmt->shifts_out) std::copy(sh.split->shifts.begin(), sh.split->shifts.end(), spec.fmt->shifts_out);
+    }
     if (sh.meter && o.out_prefix) sh.meter->write_status(std::string(o.out_prefix) + ".status");
 }
 
@@ -1275,4 +1316,22 @@ extern "C" int sdr_multi_run_rds_carrier(const sdr_multi_opts* opts, const sdr_m
     sdr_rds_track_opts defaults;
     sdr_rds_track_opts_default(&defaults);
     return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, rds_clock, track ? track : &defaults, soft, carrier}, stats);
+}
+
+extern "C" int sdr_multi_run_wide_fmt(const sdr_multi_opts* opts, const sdr_multi_wide* wide, const sdr_multi_tuning* tune,
+                                      const sdr_meter_opts* mo, const sdr_audio_opts* ao, int blend, const sdr_multi_rds* rds,
+                                      int rds_clock, const sdr_rds_track_opts* track, const sdr_rds_soft_opts* soft,
+                                      const sdr_rds_carrier_opts* carrier, const sdr_wide_fmt* fmt, sdr_multi_stats* stats) {
+    if (!sdrhost::wide16(fmt))
+        return sdr_multi_run_rds_carrier(opts, wide, tune, mo, ao, blend, rds, rds_clock, track, soft, carrier, stats);
+    if (!wide || !tune) return SDR_E_INVALID;   // int16 rows are wide rows, and a wide run is always tuned
+    // the chain of entry points below this one, with the record: each step's own refusals, then the run
+    if (rds_clock == SDR_MULTI_RDS_CLOCK_REF) {
+        if (soft || carrier) return SDR_E_INVALID;
+        return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, SDR_MULTI_RDS_CLOCK_REF, nullptr, nullptr, nullptr, fmt}, stats);
+    }
+    if (!rds) return SDR_E_INVALID;
+    sdr_rds_track_opts defaults;
+    sdr_rds_track_opts_default(&defaults);
+    return multi_run({opts, tune, mo, ao, blend != 0, wide, rds, rds_clock, track ? track : &defaults, soft, carrier, fmt}, stats);
 }

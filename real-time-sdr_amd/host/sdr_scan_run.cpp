@@ -3,14 +3,19 @@
 //   sdr_scan_run (include/sdr_scan_run.h): the blocks hold capture rows; list entry src is the row.
 //   sdr_wide_scan_run (include/sdr_wide_scan.h): the blocks hold wide streams, which sdr_split_block cuts
 //     into capture rows in front of the scanner; every row is picked on the absolute station grid.
+//   sdr_wide_scan_run_fmt (include/sdr_multi_wide16.h): the same on int16 wide streams (sdr_split16_block), with a
+//     shift per row, fixed or taken from block 0's peaks before the scan starts at block 0.
 // The plain scan is the wide one without a splitter: one row per input stream, the caller's pick options.
 #include "sdr_scan_run.h"
 #include "sdr_wide_scan.h"
+#include "sdr_multi_wide16.h"
+#include "wide16.h"
 
 #include <hip/hip_runtime_api.h>
 
 #include <cstdarg>
 #include <cstdio>
+#include <algorithm>
 #include <cstring>
 #include <set>
 #include <vector>
@@ -29,12 +34,14 @@ struct Run {
     FILE* in = nullptr;
     bool close_in = false;
     sdr_split* split = nullptr;
+    sdr_split16* split16 = nullptr;
     sdr_scan* scan = nullptr;
     uint8_t *d_in = nullptr, *d_rows = nullptr;   // the uploaded block; a wide scan's capture rows
     hipStream_t stream = nullptr;
     ~Run() {
         if (scan) sdr_scan_destroy(scan);
         if (split) sdr_split_destroy(split);
+        if (split16) sdr_split16_destroy(split16);
         if (d_in) (void)hipFree(d_in);
         if (d_rows) (void)hipFree(d_rows);
         if (stream) (void)hipStreamDestroy(stream);
@@ -43,7 +50,9 @@ struct Run {
 };
 
 // o->nwide input streams per block; wide: each is a wide stream of o->W, else a capture row (W, shift unused)
-int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st) {
+// fmt (a wide scan's only): int16 wide streams
+int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st, const sdr_wide_fmt* fmt = nullptr) {
+    const bool s16 = sdrhost::wide16(fmt);
     const char* who = wide ? "wide scan" : "scan";
     std::memset(st, 0, sizeof(*st));
     if (!o || !o->in_path || o->nwide < 1)
@@ -56,6 +65,9 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st) {
         sdr_scan_geometry(o->mode, &N, nullptr, &block_iq) != SDR_OK)
         return fail(st, SDR_E_INVALID, "%s: %s", who, sdr_last_error());
     if (!wide) in_iq = block_iq;
+    if (s16)
+        if (const char* why = sdrhost::wide_fmt_refusal(fmt, o->mode, o->W, o->nwide, o->shift))
+            return fail(st, SDR_E_INVALID, "%s: %s", who, why);
     const int max_blocks = o->max_blocks > 0 ? o->max_blocks : 4;
     const int nrows = o->nwide * R;
     Run r;
@@ -66,9 +78,11 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st) {
         r.close_in = true;
     }
     if (!r.in) return fail(st, SDR_E_INVALID, "%s: cannot open %s", who, o->in_path);
-    const size_t in_bytes = (size_t)2 * in_iq, block_bytes = in_bytes * (size_t)o->nwide;
+    const size_t in_bytes = (size_t)(s16 ? 4 : 2) * in_iq, block_bytes = in_bytes * (size_t)o->nwide;
     const size_t row_bytes = (size_t)2 * block_iq;
-    int rc = wide ? sdr_split_create(&r.split, o->device, o->mode, o->W, o->nwide, o->shift) : SDR_OK;
+    int rc = s16    ? sdr_split16_create(&r.split16, o->device, o->mode, o->W, o->nwide, o->shift)
+             : wide ? sdr_split_create(&r.split, o->device, o->mode, o->W, o->nwide, o->shift)
+                    : SDR_OK;
     if (rc == SDR_OK) rc = sdr_scan_create(&r.scan, o->device, o->mode, nrows);
     if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
     if (hipSetDevice(o->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&r.d_in), block_bytes) != hipSuccess ||
@@ -80,13 +94,26 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st) {
         return fail(st, SDR_E_HIP, "scan: no device buffer of %zu bytes or no stream", block_bytes);
     }
     std::vector<uint8_t> host(block_bytes);
+    std::vector<int> shifts;
+    if (s16) {
+        shifts.assign((size_t)nrows, o->shift > 0 ? o->shift : sdr_split16_shift_for(0, 90, o->W));
+        if (fmt->shifts) {
+            shifts.assign(fmt->shifts, fmt->shifts + nrows);
+            if (sdr_split16_set_shifts(r.split16, shifts.data(), r.stream) != SDR_OK) return fail(st, SDR_E_INVALID, "%s: %s", who, sdr_last_error());
+        }
+    }
     while (st->blocks < max_blocks && std::fread(host.data(), 1, block_bytes, r.in) == block_bytes) {
         // (the copy returns once the pageable buffer is staged; the kernels of the previous block read
         // d_in and d_rows in stream order before it)
         if (hipMemcpyAsync(r.d_in, host.data(), block_bytes, hipMemcpyHostToDevice, r.stream) != hipSuccess ||
             hipStreamSynchronize(r.stream) != hipSuccess)
             return fail(st, SDR_E_HIP, "%s: upload of block %lld failed", who, st->blocks);
-        if (wide) rc = sdr_split_block(r.split, reinterpret_cast<const int8_t*>(r.d_in), in_bytes, r.d_rows, row_bytes, r.stream);
+        if (s16) {
+            const int16_t* in16 = reinterpret_cast<const int16_t*>(r.d_in);
+            if (st->blocks == 0 && fmt->gain == SDR_WIDE_GAIN_AUTO)   // (d_rows is written again below)
+                rc = sdrhost::wide16_auto_gain(r.split16, o->W, fmt->target, in16, in_bytes, r.d_rows, row_bytes, r.stream, &shifts);
+            if (rc == SDR_OK) rc = sdr_split16_block(r.split16, in16, in_bytes, r.d_rows, row_bytes, r.stream);
+        } else if (wide) rc = sdr_split_block(r.split, reinterpret_cast<const int8_t*>(r.d_in), in_bytes, r.d_rows, row_bytes, r.stream);
         if (rc == SDR_OK) rc = sdr_scan_block(r.scan, wide ? r.d_rows : r.d_in, row_bytes, r.stream);
         if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
         st->blocks++;
@@ -97,7 +124,9 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st) {
     std::vector<float> psd((size_t)nrows * N);
     rc = sdr_scan_psd(r.scan, psd.data(), &st->segments, r.stream);
     std::vector<long long> clips((size_t)nrows);
-    if (rc == SDR_OK && wide) rc = sdr_split_clips(r.split, clips.data(), r.stream);
+    if (rc == SDR_OK && wide) rc = s16 ? sdr_split16_clips(r.split16, clips.data(), r.stream) : sdr_split_clips(r.split, clips.data(), r.stream);
+    if (rc == SDR_OK && s16 && fmt->peaks_out) rc = sdr_split16_peaks(r.split16, fmt->peaks_out, 0, r.stream);
+    if (s16 && fmt->shifts_out) std::copy(shifts.begin(), shifts.end(), fmt->shifts_out);
     if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
     for (long long c : clips) st->clips += c;
     std::vector<int32_t> src, khz, row_khz(N + 1);
@@ -140,6 +169,10 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st) {
 
 extern "C" int sdr_wide_scan_run(const sdr_wide_scan_opts* o, sdr_wide_scan_stats* st) {
     return st ? scan_file(o, true, st) : SDR_E_INVALID;
+}
+
+extern "C" int sdr_wide_scan_run_fmt(const sdr_wide_scan_opts* o, const sdr_wide_fmt* fmt, sdr_wide_scan_stats* st) {
+    return st ? scan_file(o, true, st, fmt) : SDR_E_INVALID;
 }
 
 extern "C" int sdr_scan_run(const sdr_scan_run_opts* o, sdr_scan_run_stats* st) {
