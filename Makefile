@@ -14,7 +14,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-g
 LIB      := $(PKG)/libsdr_amd.so
 SRCS     := $(PKG)/csrc/sdr_kernels.hip $(PKG)/csrc/sdr_ctx.hip $(PKG)/csrc/sdr_plls.cpp $(PKG)/csrc/sdr_streams.hip \
             $(PKG)/csrc/sdr_primitives.hip $(PKG)/csrc/sdr_frontend.hip $(PKG)/csrc/sdr_pll.hip $(PKG)/csrc/sdr_scan.hip \
-            $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip $(PKG)/csrc/sdr_split.hip $(PKG)/csrc/sdr_split16.hip \
+            $(PKG)/csrc/sdr_meter.hip $(PKG)/csrc/sdr_audio.hip $(PKG)/csrc/sdr_split.hip \
             $(PKG)/csrc/sdr_rds.hip $(PKG)/csrc/sdr_rds_track.hip $(PKG)/csrc/sdr_rds_carrier.hip \
             $(PKG)/csrc/sdr_taps.cpp $(PKG)/csrc/sdr_rds_text.cpp
 OBJS     := $(patsubst $(PKG)/csrc/%,build/%.o,$(SRCS))
@@ -27,7 +27,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wextra -pthread -D__HIP_PLATFORM_AMD__ 
 HOSTLIB   := $(PKG)/libsdr_host.so
 HOSTSRCS  := $(PKG)/host/dropin_primitives.cpp $(PKG)/host/dropin_stages.cpp $(PKG)/host/rds_frame.cpp \
              $(PKG)/host/sdr_multi_engine.cpp $(PKG)/host/sdr_scan_run.cpp
-HOSTHDRS  := $(wildcard include/dropin/*.h) $(PKG)/host/hip_util.h $(PKG)/host/wide16.h include/sdr_amd.h include/sdr_multi.h \
+HOSTHDRS  := $(wildcard include/dropin/*.h) $(PKG)/host/hip_util.h $(PKG)/host/wide_split.h include/sdr_amd.h include/sdr_multi.h \
              include/sdr_multi_tuned.h include/sdr_multi_meter.h include/sdr_multi_audio.h include/sdr_scan_run.h \
              include/sdr_multi_wide.h include/sdr_wide_scan.h include/sdr_multi_rds.h include/sdr_multi_wide16.h
 CLI       := $(PKG)/bin/sdr_project

@@ -543,39 +543,50 @@ class Splitter(_Handle):
     """`nwide` wide int8 I/Q captures at W * rf_Fs into nwide * (2 W - 1) capture rows at rf_Fs, the rows
     sdr_frontend_tuned and the Scanner read (sdr_split_*). Its own handle: no channels, any stream."""
 
-    _destroy, _reset = "sdr_split_destroy", "sdr_split_reset"
+    _c, _name, _dtype, _bytes = "sdr_split", "Splitter", "int8", 1    # the C prefix; of a value: torch dtype, bytes
+    _destroy = property(lambda self: self._c + "_destroy")
+    _reset = property(lambda self: self._c + "_reset")
 
     def __init__(self, W: int, nwide: int, mode: int = 0, device: int = 0, shift=None):
         h = C.c_void_p()
-        check(lib().sdr_split_create(C.byref(h), device, mode, W, nwide, 0 if shift is None else int(shift)),
-              "sdr_split_create")
+        create = getattr(lib(), self._c + "_create")
+        check(create(C.byref(h), device, mode, W, nwide, 0 if shift is None else int(shift)), self._c + "_create")
         self._h = h
         self.W, self.nwide, self.mode, self.device = W, nwide, mode, device
         self.rows, self.taps, self.wide_iq, self.half_khz, d = split_geometry(mode, W)
-        self.shift = d if shift is None or shift <= 0 else int(shift)
         self.block_iq = self.wide_iq // W
+        self._set_shift(d, None if shift is None or shift <= 0 else int(shift))
+
+    def _set_shift(self, d: int, shift):
+        """d: split_geometry's default shift; shift: the constructor's, or None for the default."""
+        self.shift = d if shift is None else shift
 
     def block(self, wide, out=None, stream=None):
-        """wide: int8 [nwide][2*W*block_iq] (device). Returns the uint8 rows [nwide*R][2*block_iq] (out, or
-        a new tensor); enqueues, no sync."""
+        """wide: int8 (Splitter16: int16) [nwide][2*W*block_iq] (device). Returns the uint8 rows
+        [nwide*R][2*block_iq] (out, or a new tensor); enqueues, no sync."""
         import torch
-        if wide.dim() != 2 or wide.shape[0] != self.nwide or wide.dtype != torch.int8:
-            raise SdrError(f"Splitter.block: expected int8 [{self.nwide}][2*W*block_iq] streams", -1)
+        if wide.dim() != 2 or wide.shape[0] != self.nwide or wide.dtype != getattr(torch, self._dtype):
+            raise SdrError(f"{self._name}.block: expected {self._dtype} [{self.nwide}][2*W*block_iq] streams", -1)
         if out is None:
             out = torch.empty((self.nwide * self.rows, 2 * self.block_iq), dtype=torch.uint8, device=wide.device)
         elif out.dim() != 2 or out.shape[0] != self.nwide * self.rows or out.dtype != torch.uint8:
-            raise SdrError(f"Splitter.block: expected uint8 [{self.nwide * self.rows}][2*block_iq] rows", -1)
+            raise SdrError(f"{self._name}.block: expected uint8 [{self.nwide * self.rows}][2*block_iq] rows", -1)
         ws = _row_stride(wide) if wide.shape[0] > 1 else int(wide.shape[1])
-        check(lib().sdr_split_block(self._h, _ptr(wide), ws, _ptr(out), _row_stride(out), _stream(stream)),
-              "sdr_split_block")
+        check(getattr(lib(), self._c + "_block")(self._h, _ptr(wide), self._bytes * ws, _ptr(out), _row_stride(out),
+                                                 _stream(stream)), self._c + "_block")
         return out
+
+    def _read(self, what, *args, stream=None):
+        """numpy int64 [nwide][R] of sdr_split*_<what>; synchronises the stream."""
+        import numpy as np
+        c = np.zeros((self.nwide, self.rows), np.int64)
+        check(getattr(lib(), f"{self._c}_{what}")(self._h, c.ctypes.data_as(C.c_void_p), *args, _stream(stream)),
+              f"{self._c}_{what}")
+        return c
 
     def clips(self, stream=None):
         """numpy int64 [nwide][R]: clipped output components since the last reset; synchronises the stream."""
-        import numpy as np
-        c = np.zeros((self.nwide, self.rows), np.int64)
-        check(lib().sdr_split_clips(self._h, c.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_split_clips")
-        return c
+        return self._read("clips", stream=stream)
 
 
 def split16_shift_for(peak: int, target: int = 90, *, W: int) -> int:
@@ -587,24 +598,16 @@ def split16_shift_for(peak: int, target: int = 90, *, W: int) -> int:
     return s
 
 
-class Splitter16(_Handle):
+class Splitter16(Splitter):
     """The Splitter for wide int16 I/Q captures (sdr_split16_*): a shift per stream and row (set_shifts) and a
     peak reading per row (peaks), so that each row can have its own gain. Its own handle: any stream."""
 
-    _destroy, _reset = "sdr_split16_destroy", "sdr_split16_reset"
+    _c, _name, _dtype, _bytes = "sdr_split16", "Splitter16", "int16", 2
 
-    def __init__(self, W: int, nwide: int, mode: int = 0, device: int = 0, shift=None):
+    def _set_shift(self, d: int, shift):
         import numpy as np
-        h = C.c_void_p()
-        check(lib().sdr_split16_create(C.byref(h), device, mode, W, nwide, 0 if shift is None else int(shift)),
-              "sdr_split16_create")
-        self._h = h
-        self.W, self.nwide, self.mode, self.device = W, nwide, mode, device
-        self.rows, self.taps, self.wide_iq, self.half_khz, d = split_geometry(mode, W)
         self.shift_default = d + 8
-        self.block_iq = self.wide_iq // W
-        self._shifts = np.full((nwide, self.rows), self.shift_default if shift is None or shift <= 0 else int(shift),
-                               np.int32)
+        self._shifts = np.full((self.nwide, self.rows), self.shift_default if shift is None else shift, np.int32)
 
     @property
     def shifts(self):
@@ -622,36 +625,10 @@ class Splitter16(_Handle):
               "sdr_split16_set_shifts")
         self._shifts = t.reshape(self.nwide, self.rows).copy()
 
-    def block(self, wide, out=None, stream=None):
-        """wide: int16 [nwide][2*W*block_iq] (device). Returns the uint8 rows [nwide*R][2*block_iq] (out, or
-        a new tensor); enqueues, no sync."""
-        import torch
-        if wide.dim() != 2 or wide.shape[0] != self.nwide or wide.dtype != torch.int16:
-            raise SdrError(f"Splitter16.block: expected int16 [{self.nwide}][2*W*block_iq] streams", -1)
-        if out is None:
-            out = torch.empty((self.nwide * self.rows, 2 * self.block_iq), dtype=torch.uint8, device=wide.device)
-        elif out.dim() != 2 or out.shape[0] != self.nwide * self.rows or out.dtype != torch.uint8:
-            raise SdrError(f"Splitter16.block: expected uint8 [{self.nwide * self.rows}][2*block_iq] rows", -1)
-        ws = _row_stride(wide) if wide.shape[0] > 1 else int(wide.shape[1])
-        check(lib().sdr_split16_block(self._h, _ptr(wide), 2 * ws, _ptr(out), _row_stride(out), _stream(stream)),
-              "sdr_split16_block")
-        return out
-
-    def clips(self, stream=None):
-        """numpy int64 [nwide][R]: clipped output components since the last reset; synchronises the stream."""
-        import numpy as np
-        c = np.zeros((self.nwide, self.rows), np.int64)
-        check(lib().sdr_split16_clips(self._h, c.ctypes.data_as(C.c_void_p), _stream(stream)), "sdr_split16_clips")
-        return c
-
     def peaks(self, clear: bool = False, stream=None):
         """numpy int64 [nwide][R]: the largest |acc_re| or |acc_im| of each row since the last reset or clearing
         read (clear=True makes this one); independent of the shifts; synchronises the stream."""
-        import numpy as np
-        p = np.zeros((self.nwide, self.rows), np.int64)
-        check(lib().sdr_split16_peaks(self._h, p.ctypes.data_as(C.c_void_p), 1 if clear else 0, _stream(stream)),
-              "sdr_split16_peaks")
-        return p
+        return self._read("peaks", 1 if clear else 0, stream=stream)
 
 
 # ------------------------------------------------------------------ reception meter (include/sdr_amd.h, sdr_meter_*)

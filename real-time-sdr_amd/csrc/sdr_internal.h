@@ -11,8 +11,8 @@
 //   stage_host.h       host code shared by the units below that own a handle: create, destroy, reset, record reads
 //   sdr_scan.hip       band scan of the capture rows
 //   sdr_meter.hip      reception meter: per-channel readings of a block's rows
-//   sdr_split.hip      wideband splitter: a wide s8 capture into the capture rows (its own handle)
-//   sdr_split16.hip    its 16-bit sibling: a wide int16 capture, a shift and a peak reading per row (its own handle)
+//   sdr_split.hip      wideband splitters: a wide s8 capture into the capture rows, and the 16-bit sibling for a wide
+//                      int16 capture with a shift and a peak reading per row (a handle each)
 //   sdr_rds.hip        RDS group decoder over the bits of sdr_rds_bits or the tracker (its own handle); with the
 //                      tracker's soft values, a search over a failing block's least reliable bits (sdr_rds_*_soft)
 //   sdr_rds_track.hip  RDS symbol tracker: rds_clean rows into bits on a continuous bit clock (its own handle),

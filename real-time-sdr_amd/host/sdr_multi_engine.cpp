@@ -87,7 +87,7 @@
 #include "sdr_multi_tuned.h"
 #include "sdr_multi_wide.h"
 #include "sdr_multi_wide16.h"
-#include "wide16.h"
+#include "wide_split.h"
 
 using sdrhost::check_hip;
 using sdrhost::check_sdr;
@@ -582,45 +582,8 @@ struct AudioFin {
     ~AudioFin() { (void)sdr_audio_destroy(a); }
 };
 
-// A wide run's splitter and its geometry: nwide * (2 W - 1) capture rows per block from rows of 2 * wide_iq bytes
-// (int8 streams, s) or 4 * wide_iq bytes (int16 streams, s16: a shift per row, fixed or from block 0's peaks)
-struct Splitter {
-    sdr_split* s = nullptr;
-    sdr_split16* s16 = nullptr;
-    int rows = 0, wide_iq = 0, W = 0;
-    size_t in_row = 0;                   // bytes of a wide stream's block
-    int auto_target = -1;                // >= 0: the shifts come from block 0 (0: the default target)
-    std::vector<int> shifts;             // s16: the table in use
-    Splitter(const sdr_multi_opts& o, const sdr_multi_wide& w, const sdr_wide_fmt* f) : W(w.W) {
-        check_sdr(sdr_split_geometry(o.mode, w.W, &rows, nullptr, &wide_iq, nullptr, nullptr), "sdr_split_geometry");
-        rows *= w.nwide;
-        in_row = (sdrhost::wide16(f) ? 4 : 2) * (size_t)wide_iq;
-        if (!sdrhost::wide16(f)) {
-            check_sdr(sdr_split_create(&s, o.device, o.mode, w.W, w.nwide, w.shift), "sdr_split_create");
-            return;
-        }
-        check_sdr(sdr_split16_create(&s16, o.device, o.mode, w.W, w.nwide, w.shift), "sdr_split16_create");
-        shifts.assign((size_t)rows, w.shift > 0 ? w.shift : sdr_split16_shift_for(0, 90, w.W));
-        if (f->shifts) {
-            shifts.assign(f->shifts, f->shifts + rows);
-            check_sdr(sdr_split16_set_shifts(s16, shifts.data(), nullptr), "sdr_split16_set_shifts");
-        }
-        if (f->gain == SDR_WIDE_GAIN_AUTO) auto_target = f->target;
-    }
-    // block 0 of an auto gain run, in front of its block call: the shifts from its peaks (scratch: rows nobody reads)
-    void gain_from(const uint8_t* src, size_t stride, uint8_t* scratch, size_t row, hipStream_t st) {
-        check_sdr(sdrhost::wide16_auto_gain(s16, W, auto_target, reinterpret_cast<const int16_t*>(src), stride, scratch, row,
-                                            st, &shifts), "the wide run's auto gain");
-    }
-    void block(const uint8_t* src, size_t stride, uint8_t* out, size_t row, hipStream_t st) {
-        if (s16) check_sdr(sdr_split16_block(s16, reinterpret_cast<const int16_t*>(src), stride, out, row, st), "sdr_split16_block");
-        else check_sdr(sdr_split_block(s, reinterpret_cast<const int8_t*>(src), stride, out, row, st), "sdr_split_block");
-    }
-    ~Splitter() {
-        if (s) (void)sdr_split_destroy(s);
-        if (s16) (void)sdr_split16_destroy(s16);
-    }
-};
+// the code of a call of the wide run's splitter (host/wide_split.h), behind the name of the C call that failed
+void check_split(const sdrhost::WideSplit& s, int rc) { check_sdr(rc, s.failed); }
 
 // a recycled device batch of fm_demod [nch][block_if] and its events (include/dropin/fm_batch.h)
 struct Batch {
@@ -672,7 +635,7 @@ struct Shared : NoCopy {
     Stream s_all;
     Event ev_first[3], ev_last[3];
     Ctx ctx[3];                          // RF, audio, RDS (each thread owns its context)
-    std::optional<Splitter> split;       // a wide run: the input rows are wide int8 streams
+    std::optional<sdrhost::WideSplit> split;   // a wide run: the input rows are wide int8 or int16 streams
     std::optional<AudioRes> ar;
     std::optional<RdsRes> rr;
     std::optional<MeterOut> meter;       // a metered run
@@ -815,8 +778,9 @@ void rf_thread(Shared* sh) {
         if (sh->split) {
             const int k = (int)(b & 1);
             if (b >= 2) check_hip(hipStreamWaitEvent(sf, rows_done[k], 0), "hipStreamWaitEvent");
-            if (b == 0 && sh->split->auto_target >= 0) sh->split->gain_from(src, stride, d_rows[1].p, row, sf);
-            sh->split->block(src, stride, d_rows[k].p, row, sf);
+            if (b == 0 && sh->split->auto_target >= 0)   // (scratch: the buffer block 1 writes)
+                check_split(*sh->split, sh->split->gain_from(src, stride, d_rows[1].p, row, sf));
+            check_split(*sh->split, sh->split->block(src, stride, d_rows[k].p, row, sf));
             check_sdr(sdr_frontend_tuned(ctx, d_rows[k].p, row, sf), "sdr_frontend_tuned");
             check_hip(hipEventRecord(rows_done[k], sf), "hipEventRecord");
         } else if (sh->tuned) check_sdr(sdr_frontend_tuned(ctx, src, stride, sf), "sdr_frontend_tuned");
@@ -1144,7 +1108,10 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
         check_sdr(spec.tune ? sdr_tuner_set(c, spec.tune->nsrc, spec.tune->src, spec.tune->khz, nullptr)
                             : sdr_tuner_set(c, 0, nullptr, nullptr, nullptr), "sdr_tuner_set");
     check_sdr(sdr_ctx_info(sh.ctx[0], &sh.info), "sdr_ctx_info");
-    if (spec.wide) sh.split.emplace(o, *spec.wide, spec.fmt);
+    if (const sdr_multi_wide* w = spec.wide) {
+        sh.split.emplace();
+        check_split(*sh.split, sh.split->open(o.device, o.mode, w->W, w->nwide, w->shift, spec.fmt, nullptr));
+    }
     sh.in_row = spec.wide ? sh.split->in_row : 2 * (size_t)sh.info.block_iq;
     sh.nblocks_known = o.in_path ? regular_file_blocks(o.in_path, sh.in_row * (size_t)sh.rows) : o.nblocks;
     // streams: the PLLs on [0, pll_cus) (halves), everything else on the rest
@@ -1232,13 +1199,7 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     // The one order that matters at the end: the device is idle before sh releases anything, and the
     // splitter's clip counters are read while the splitter exists.
     check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    if (sh.split && sh.split->s && spec.wide->clips)
-        check_sdr(sdr_split_clips(sh.split->s, spec.wide->clips, nullptr), "sdr_split_clips");
-    if (sh.split && sh.split->s16) {
-        if (spec.wide->clips) check_sdr(sdr_split16_clips(sh.split->s16, spec.wide->clips, nullptr), "sdr_split16_clips");
-        if (spec.fmt->peaks_out) check_sdr(sdr_split16_peaks(sh.split->s16, spec.fmt->peaks_out, 0, nullptr), "sdr_split16_peaks");
-        if (spec.fmt->shifts_out) std::copy(sh.split->shifts.begin(), sh.split->shifts.end(), spec.fmt->shifts_out);
-    }
+    if (sh.split) check_split(*sh.split, sh.split->report(spec.wide->clips, spec.fmt, nullptr));
     if (sh.meter && o.out_prefix) sh.meter->write_status(std::string(o.out_prefix) + ".status");
 }
 

@@ -9,7 +9,7 @@
 #include "sdr_scan_run.h"
 #include "sdr_wide_scan.h"
 #include "sdr_multi_wide16.h"
-#include "wide16.h"
+#include "wide_split.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -33,15 +33,13 @@ int fail(sdr_wide_scan_stats* st, int code, const char* fmt, ...) {
 struct Run {
     FILE* in = nullptr;
     bool close_in = false;
-    sdr_split* split = nullptr;
-    sdr_split16* split16 = nullptr;
+    sdrhost::WideSplit split;                     // a wide scan's
     sdr_scan* scan = nullptr;
     uint8_t *d_in = nullptr, *d_rows = nullptr;   // the uploaded block; a wide scan's capture rows
     hipStream_t stream = nullptr;
     ~Run() {
         if (scan) sdr_scan_destroy(scan);
-        if (split) sdr_split_destroy(split);
-        if (split16) sdr_split16_destroy(split16);
+        split.close();
         if (d_in) (void)hipFree(d_in);
         if (d_rows) (void)hipFree(d_rows);
         if (stream) (void)hipStreamDestroy(stream);
@@ -80,9 +78,7 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st, c
     if (!r.in) return fail(st, SDR_E_INVALID, "%s: cannot open %s", who, o->in_path);
     const size_t in_bytes = (size_t)(s16 ? 4 : 2) * in_iq, block_bytes = in_bytes * (size_t)o->nwide;
     const size_t row_bytes = (size_t)2 * block_iq;
-    int rc = s16    ? sdr_split16_create(&r.split16, o->device, o->mode, o->W, o->nwide, o->shift)
-             : wide ? sdr_split_create(&r.split, o->device, o->mode, o->W, o->nwide, o->shift)
-                    : SDR_OK;
+    int rc = wide ? r.split.create(o->device, o->mode, o->W, o->nwide, o->shift, fmt) : SDR_OK;
     if (rc == SDR_OK) rc = sdr_scan_create(&r.scan, o->device, o->mode, nrows);
     if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
     if (hipSetDevice(o->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&r.d_in), block_bytes) != hipSuccess ||
@@ -93,27 +89,17 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st, c
                         row_bytes * (size_t)nrows);
         return fail(st, SDR_E_HIP, "scan: no device buffer of %zu bytes or no stream", block_bytes);
     }
+    if (wide && r.split.set_table(fmt, r.stream) != SDR_OK) return fail(st, SDR_E_INVALID, "%s: %s", who, sdr_last_error());
     std::vector<uint8_t> host(block_bytes);
-    std::vector<int> shifts;
-    if (s16) {
-        shifts.assign((size_t)nrows, o->shift > 0 ? o->shift : sdr_split16_shift_for(0, 90, o->W));
-        if (fmt->shifts) {
-            shifts.assign(fmt->shifts, fmt->shifts + nrows);
-            if (sdr_split16_set_shifts(r.split16, shifts.data(), r.stream) != SDR_OK) return fail(st, SDR_E_INVALID, "%s: %s", who, sdr_last_error());
-        }
-    }
     while (st->blocks < max_blocks && std::fread(host.data(), 1, block_bytes, r.in) == block_bytes) {
         // (the copy returns once the pageable buffer is staged; the kernels of the previous block read
         // d_in and d_rows in stream order before it)
         if (hipMemcpyAsync(r.d_in, host.data(), block_bytes, hipMemcpyHostToDevice, r.stream) != hipSuccess ||
             hipStreamSynchronize(r.stream) != hipSuccess)
             return fail(st, SDR_E_HIP, "%s: upload of block %lld failed", who, st->blocks);
-        if (s16) {
-            const int16_t* in16 = reinterpret_cast<const int16_t*>(r.d_in);
-            if (st->blocks == 0 && fmt->gain == SDR_WIDE_GAIN_AUTO)   // (d_rows is written again below)
-                rc = sdrhost::wide16_auto_gain(r.split16, o->W, fmt->target, in16, in_bytes, r.d_rows, row_bytes, r.stream, &shifts);
-            if (rc == SDR_OK) rc = sdr_split16_block(r.split16, in16, in_bytes, r.d_rows, row_bytes, r.stream);
-        } else if (wide) rc = sdr_split_block(r.split, reinterpret_cast<const int8_t*>(r.d_in), in_bytes, r.d_rows, row_bytes, r.stream);
+        if (wide && st->blocks == 0 && r.split.auto_target >= 0)   // (d_rows is written again below)
+            rc = r.split.gain_from(r.d_in, in_bytes, r.d_rows, row_bytes, r.stream);
+        if (wide && rc == SDR_OK) rc = r.split.block(r.d_in, in_bytes, r.d_rows, row_bytes, r.stream);
         if (rc == SDR_OK) rc = sdr_scan_block(r.scan, wide ? r.d_rows : r.d_in, row_bytes, r.stream);
         if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
         st->blocks++;
@@ -124,9 +110,7 @@ int scan_file(const sdr_wide_scan_opts* o, bool wide, sdr_wide_scan_stats* st, c
     std::vector<float> psd((size_t)nrows * N);
     rc = sdr_scan_psd(r.scan, psd.data(), &st->segments, r.stream);
     std::vector<long long> clips((size_t)nrows);
-    if (rc == SDR_OK && wide) rc = s16 ? sdr_split16_clips(r.split16, clips.data(), r.stream) : sdr_split_clips(r.split, clips.data(), r.stream);
-    if (rc == SDR_OK && s16 && fmt->peaks_out) rc = sdr_split16_peaks(r.split16, fmt->peaks_out, 0, r.stream);
-    if (s16 && fmt->shifts_out) std::copy(shifts.begin(), shifts.end(), fmt->shifts_out);
+    if (rc == SDR_OK && wide) rc = r.split.report(clips.data(), fmt, r.stream);
     if (rc != SDR_OK) return fail(st, rc, "%s: %s", who, sdr_last_error());
     for (long long c : clips) st->clips += c;
     std::vector<int32_t> src, khz, row_khz(N + 1);

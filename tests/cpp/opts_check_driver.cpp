@@ -1,5 +1,7 @@
 // opts_check_driver.cpp -- every sdr_*_check function of libsdr_amd.so (include/sdr_amd.h) over the grid of
-// tests/test_opts_check.py, and a NULL for each pointer argument: a stand-alone program for a sanitizer run of
+// tests/test_opts_check.py, and a NULL for each pointer argument; the 16-bit splitter's gain rule at its ends; and
+// the splitters' tap table (sdr_split_taps) and, through the creates on a device that does not exist, the tap
+// fragments and column sums built from it: a stand-alone program for a sanitizer run of
 // the library's host code. The checks are host arithmetic, so it runs on a machine without a GPU. Build it with
 // the library's translation units, all with the sanitizer on the host side only, and run it:
 //   for f in real-time-sdr_amd/csrc/*.hip real-time-sdr_amd/csrc/*.cpp tests/cpp/opts_check_driver.cpp; do
@@ -10,8 +12,10 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <initializer_list>
 #include <limits>
+#include <vector>
 
 #include "sdr_amd.h"
 
@@ -70,6 +74,11 @@ int main() {
                 for (int sh : {-1, 0, 1, 13, 24, 25})
                     expect(sdr_split_check(mode, W, nw, sh), mok && (W == 4 || W == 8 || W == 10) && nw >= 1 && nw <= 4096 && sh <= 24,
                            "split", mode);
+        for (int W : {3, 4, 5, 8, 10, 11})
+            for (int nw : {0, 1, 4096, 4097})
+                for (int sh : {-1, 0, 1, 22, 33, 34})
+                    expect(sdr_split16_check(mode, W, nw, sh), mok && (W == 4 || W == 8 || W == 10) && nw >= 1 && nw <= 4096 && sh <= 33,
+                           "split16", mode);
         const int half = mode == 0 || mode == 2 ? 1200 : mode == 1 ? 720 : mode == 3 ? 576 : 0;   // rf_Fs / 2000
         constexpr int NCH = 3;
         for (int nsrc : {-1, 0, 1, 2, NCH, NCH + 1})
@@ -85,6 +94,48 @@ int main() {
         expect(sdr_tuner_check(mode, NCH, 1, nullptr, z), false, "tuner NULL src", mode);
         expect(sdr_tuner_check(mode, NCH, 1, z, nullptr), false, "tuner NULL khz", mode);
         expect(sdr_tuner_check(mode, NCH, 0, nullptr, nullptr), mok, "tuner untuned", mode);
+    }
+    for (int W : {4, 8, 10}) {
+        // the smallest shift in 1..32 at which the peak rounds to at most the target, else 33; W's default for a peak of 0
+        for (long long peak : {0LL, 1LL, 1LL << 31, (1LL << 33) - 1})
+            for (int target : {1, 90, 127}) {
+                int want = peak == 0 ? (W == 4 ? 22 : W == 8 ? 23 : 24) : 33;
+                for (int s = 32; s >= 1 && peak > 0; s--)
+                    if (((peak + (1LL << (s - 1))) >> s) <= target) want = s;
+                const int s = sdr_split16_shift_for(peak, target, W);
+                accepted++;
+                if (s != want) {
+                    std::printf("WRONG split16_shift_for(%lld, %d, %d) = %d, not %d\n", peak, target, W, s, want);
+                    wrong++;
+                }
+            }
+        expect(sdr_split16_shift_for(1, 90, W + 1), false, "split16_shift_for W", 0);
+        expect(sdr_split16_shift_for(1, 0, W), false, "split16_shift_for target 0", 0);
+        expect(sdr_split16_shift_for(1, 128, W), false, "split16_shift_for target 128", 0);
+        expect(sdr_split16_shift_for(-1, 90, W), false, "split16_shift_for negative peak", 0);
+        // the table: the count first, then the pairs into a vector of exactly that size (a builder that writes
+        // past R T pairs is the sanitizer's to find), one pair too few refused, 14-bit entries
+        int n = 0;
+        expect(sdr_split_taps(W, nullptr, 0, &n), true, "split_taps count", 0);
+        expect(sdr_split_taps(W, nullptr, 0, nullptr), false, "split_taps NULL n", 0);
+        std::vector<int16_t> g((size_t)2 * n);
+        expect(sdr_split_taps(W, g.data(), n - 1, &n), false, "split_taps short", 0);
+        expect(sdr_split_taps(W, g.data(), n, &n), true, "split_taps", 0);
+        int big = 0;
+        for (int16_t e : g) big = std::abs((int)e) > big ? std::abs((int)e) : big;
+        if (n != (2 * W - 1) * 16 * W || big == 0 || big > 8191) {
+            std::printf("WRONG split_taps(%d): %d pairs, largest entry %d\n", W, n, big);
+            wrong++;
+        }
+        // the tap fragments and the column sums: both creates build them from the table in front of their first
+        // HIP call, which refuses device -1
+        sdr_split* s8 = nullptr;
+        sdr_split16* s16 = nullptr;
+        const int rc8 = sdr_split_create(&s8, -1, 0, W, 2, 0), rc16 = sdr_split16_create(&s16, -1, 0, W, 2, 0);
+        if (rc8 != SDR_E_HIP || rc16 != SDR_E_HIP || s8 || s16) {
+            std::printf("WRONG creates on device -1 (W %d): rc %d and %d\n", W, rc8, rc16);
+            wrong++;
+        }
     }
     std::printf("opts_check_driver: %d accepted, %d refused, %d wrong\n", accepted, refused, wrong);
     return wrong ? 1 : 0;

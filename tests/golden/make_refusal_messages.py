@@ -6,7 +6,8 @@ record(L) runs the cases on a loaded library and returns {case: [code, text]}; t
 compares a build's record with the fixture, byte for byte. No case reaches a HIP call: a refused create
 stops at its checks, and a refused call stops before its handle is used, so zeroed memory stands in for one.
 The texts hold numbers only, no addresses. Recorded from the library of the commit before the stage files
-moved onto csrc/stage_host.h; run it again only when a text is meant to change:
+moved onto csrc/stage_host.h; the splitters' check, block, clips and 16-bit cases from the commit before
+csrc/sdr_split16.hip moved into csrc/sdr_split.hip. Run it again only when a text is meant to change:
   python tests/golden/make_refusal_messages.py [path/to/libsdr_amd.so]
 """
 from __future__ import annotations
@@ -152,6 +153,48 @@ def record(L: C.CDLL) -> dict[str, list]:
     grs("misaligned soft", t, n_, b_, sz(256), off(s_, 1), sz(256), None)
     grs("hard handle", t, n_, b_, sz(256), s_, sz(256), None)      # zeroed: not a soft handle
     assert bytes(stand_in) == bytes(256) and nb[0] == 0
+
+    # ---- the 16-bit splitter (recorded before it shared the 8-bit splitter's unit and argument rule)
+    case("split16_create/out", "sdr_split16_create", None, 0, 0, 4, 1, 0)
+    for a in ((4, 4, 1, 0), (-1, 4, 1, 0), (0, 5, 1, 0), (0, 0, 1, 0), (0, 4, 0, 0), (0, 8, 4097, 0), (0, 10, 1, 34),
+              (3, 4, 4096, 34)):
+        case(f"split16_create/mode,W,nwide,shift={a}", "sdr_split16_create", ref(h), 0, *a)
+        case(f"split16_check/mode,W,nwide,shift={a}", "sdr_split16_check", *a)
+    assert h.value is None
+    ll = C.c_longlong
+    for a in ((100, 90, 5), (100, 90, 0), (100, 0, 4), (100, 128, 8), (-1, 90, 10)):
+        case(f"split16_shift_for/peak,target,W={a}", "sdr_split16_shift_for", ll(a[0]), a[1], a[2])
+    case("split16_destroy/null", "sdr_split16_destroy", None)
+    case("split16_reset/null", "sdr_split16_reset", None, None)
+    case("split16_set_shifts/null", "sdr_split16_set_shifts", None, ints(24), None)
+    case("split16_block/null", "sdr_split16_block", None, x, sz(8), y, sz(8), None)
+    case("split16_clips/null", "sdr_split16_clips", None, x, None)
+    case("split16_peaks/null", "sdr_split16_peaks", None, x, 0, None)
+    # on the stand-in: null arguments, which stop in front of the handle, and strides and pointers that a block
+    # of any size refuses (the texts hold W and block_iq of the handle, 0 of a zeroed one)
+    case("split16_set_shifts/shifts", "sdr_split16_set_shifts", t, None, None)
+    case("split16_block/wide", "sdr_split16_block", t, None, sz(8), y, sz(8), None)
+    case("split16_block/rows", "sdr_split16_block", t, x, sz(8), None, sz(8), None)
+    case("split16_block/wide_stride", "sdr_split16_block", t, x, sz(6), y, sz(8), None)
+    case("split16_block/misaligned wide", "sdr_split16_block", t, off(x, 2), sz(8), y, sz(8), None)
+    case("split16_block/row_stride", "sdr_split16_block", t, x, sz(8), y, sz(7), None)
+    case("split16_block/misaligned rows", "sdr_split16_block", t, x, sz(8), off(y, 1), sz(8), None)
+    case("split16_clips/clips", "sdr_split16_clips", t, None, None)
+    case("split16_peaks/peaks", "sdr_split16_peaks", t, None, 0, None)
+    # ---- the 8-bit splitter's cases that its shared rules now answer
+    for a in ((4, 4, 1, 0), (-1, 4, 1, 0), (0, 5, 1, 0), (0, 0, 1, 0), (0, 4, 0, 0), (0, 8, 4097, 0), (0, 10, 1, 25),
+              (3, 4, 4096, 25)):
+        case(f"split_check/mode,W,nwide,shift={a}", "sdr_split_check", *a)
+    case("split_block/null", "sdr_split_block", None, x, sz(8), y, sz(8), None)
+    case("split_clips/null", "sdr_split_clips", None, x, None)
+    case("split_block/wide", "sdr_split_block", t, None, sz(8), y, sz(8), None)
+    case("split_block/rows", "sdr_split_block", t, x, sz(8), None, sz(8), None)
+    case("split_block/wide_stride", "sdr_split_block", t, x, sz(6), y, sz(8), None)
+    case("split_block/misaligned wide", "sdr_split_block", t, off(x, 2), sz(8), y, sz(8), None)
+    case("split_block/row_stride", "sdr_split_block", t, x, sz(8), y, sz(7), None)
+    case("split_block/misaligned rows", "sdr_split_block", t, x, sz(8), off(y, 1), sz(8), None)
+    case("split_clips/clips", "sdr_split_clips", t, None, None)
+    assert bytes(stand_in) == bytes(256)
     return out
 
 

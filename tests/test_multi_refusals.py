@@ -294,3 +294,10 @@ def test_wide_scan_run_refuses(host, pkg, tmp_path):
     assert text.startswith("wide scan: ") and "mode" in text, text
     for W in (4, 8, 10):
         refused(WO(nwide=1, W=W, in_path=path, pick=pick), f"wide scan: cannot open {missing}")
+    # behind the open and in front of every device call: the splitter's own argument rule, in its own words
+    there = tmp_path / "short_capture.s8"
+    there.write_bytes(bytes(16))
+    path = str(there).encode()
+    refused(WO(nwide=1, W=4, shift=25, in_path=path, pick=pick), "wide scan: split_create: shift 25 outside [1, 24]")
+    refused(WO(nwide=4097, W=10, in_path=path, pick=pick), "wide scan: split_create: nwide 4097 outside [1, 4096]")
+    refused(WO(nwide=4097, W=4, in_path=path, pick=pick), "wide scan: split_create: nwide 4097 outside [1, 4096]")
