@@ -146,17 +146,26 @@ int sdr_fm_demod_phase(float *out, size_t out_stride, const float *I, const floa
 int sdr_fmpll(float *out, size_t out_stride, const float *in, size_t in_stride, int nch, int n, float freq,
               float Fs, sdr_pll_state *state, float ncoScale, float phaseAdjust, float normBandwidth,
               void *stream);
-/* cdr(sps, signal): rds_utilities.cpp:4-21 (include/rds_utilities.h:6). offset: [nch] int32. */
+/* cdr(sps, signal): rds_utilities.cpp:4-21 (include/rds_utilities.h:6). offset: [nch] int32.
+ * 1 <= sps <= 64, n >= 0; offset i sums the n/sps samples x[k*sps + i]. Each sample is truncated toward
+ * zero to int32, where NaN, infinities and values outside int32 count as INT32_MIN; the per-offset sum
+ * of the magnitudes is 32 bits and wraps; an offset wins only with a sum > 0 (as int32), the lowest
+ * offset wins among equal sums, and the result is 0 when no offset wins. */
 int sdr_cdr(int32_t *offset, const float *x, size_t x_stride, int nch, int n, int sps, void *stream);
 /* manchester_decode(bits, symbols, block_count, half_symbol, start): rds_utilities.cpp:34-68
  * (include/rds_utilities.h:12). symbols [nch][sym_stride] 0/1 bytes with nsym[ch] valid;
  * state [nch][2] = {half_symbol, start} updated in place; bits [nch][bits_stride] 0/1 bytes,
- * nbits[ch] written. block_count as in the reference (0 selects the alignment search). */
+ * nbits[ch] written. block_count as in the reference (0 selects the alignment search).
+ * A call writes at most nsym[ch]/2 + 1 bits per channel (the carried half symbol plus
+ * floor(nsym[ch]/2)), so bits_stride >= max nsym/2 + 1. A channel with nsym[ch] <= 0 consumes
+ * nothing: nbits[ch] = 0, its {half_symbol, start} stay as they are and no byte of its bits row is
+ * written (the reference is undefined there). */
 int sdr_manchester_decode(uint8_t *bits, size_t bits_stride, int32_t *nbits, const uint8_t *symbols,
                           size_t sym_stride, const int32_t *nsym, int nch, int block_count, int32_t *state,
                           void *stream);
 /* differential_decode(out, bits, last_bit, block_num): rds_utilities.cpp:70-88
- * (include/rds_utilities.h:14). last_bit [nch] int32 updated in place. */
+ * (include/rds_utilities.h:14). last_bit [nch] int32 updated in place. Where nbits[ch] <= 0, out and
+ * last_bit[ch] are left untouched. */
 int sdr_differential_decode(uint8_t *out, size_t out_stride, const uint8_t *bits, size_t bits_stride,
                             const int32_t *nbits, int nch, int block_num, int32_t *last_bit, void *stream);
 

@@ -160,6 +160,28 @@ def cdr(sps, x):
     return lib().orc_cdr(sps, x, len(x))
 
 
+def manchester(symbols, block_count, state):
+    """state: two-element list [half_symbol, start], updated in place. Returns the bits (int32).
+    len(symbols) must be >= 1: the reference reads symbols[-1] for an empty row with start set."""
+    symbols = np.ascontiguousarray(symbols, np.int32)
+    if len(symbols) < 1:
+        raise ValueError("manchester: the reference is undefined for an empty row")
+    bits = np.zeros(len(symbols) // 2 + 1, np.int32)
+    half, start = C.c_int(int(state[0])), C.c_int(int(state[1]))
+    nb = lib().orc_manchester(bits, symbols, len(symbols), int(block_count), C.byref(half), C.byref(start))
+    state[0], state[1] = half.value, start.value
+    return bits[:nb].copy()
+
+
+def differential(bits, block_num, last):
+    """Returns (out, new last bit); out is empty and last unchanged for an empty `bits`."""
+    bits = np.ascontiguousarray(bits, np.int32)
+    out = np.zeros(max(len(bits), 1), np.int32)
+    lb = C.c_int(int(last))
+    lib().orc_differential(out, bits if len(bits) else out, len(bits), C.byref(lb), int(block_num))
+    return out[:len(bits)].copy(), lb.value
+
+
 # ---------------------------------------------------------------- per-channel pipeline
 class Channel:
     """One channel of the reference pipeline (RF_frontend + mono + stereo + rds), block by block."""

@@ -184,6 +184,8 @@ def lib() -> C.CDLL:
         "sdr_meter_deviation": ([i32, C.POINTER(MeterRow)] + [C.POINTER(C.c_double)] * 3, i32),
         "sdr_fmpll": ([vp, sz, vp, sz, i32, i32, f32, f32, vp, f32, f32, f32, vp], i32),
         "sdr_cdr": ([vp, vp, sz, i32, i32, i32, vp], i32),
+        "sdr_manchester_decode": ([vp, sz, vp, vp, sz, vp, i32, i32, vp, vp], i32),
+        "sdr_differential_decode": ([vp, sz, vp, sz, vp, i32, i32, vp, vp], i32),
         "sdr_ctx_create": ([C.POINTER(vp), i32, i32, i32, i32, i32], i32),
         "sdr_ctx_destroy": ([vp], i32),
         "sdr_ctx_reset": ([vp, vp], i32),
@@ -1166,6 +1168,25 @@ def cdr(offset, x, sps: int, stream=None):
     nch, n = x.shape
     check(lib().sdr_cdr(_ptr(offset), _ptr(x), _row_stride(x), nch, n, sps, _stream(stream)), "cdr")
     return offset
+
+
+def manchester_decode(bits, nbits, symbols, nsym, block_count: int, state, stream=None):
+    """manchester_decode for every row: symbols[nch][>= nsym[ch]] 0/1 uint8, nsym[nch] int32,
+    state[nch][2] int32 = {half_symbol, start} updated in place; bits[nch][>= nsym/2 + 1] uint8 and
+    nbits[nch] int32 are written. A row with nsym <= 0 gets nbits = 0 and nothing else."""
+    nch = symbols.shape[0]
+    check(lib().sdr_manchester_decode(_ptr(bits), _row_stride(bits), _ptr(nbits), _ptr(symbols), _row_stride(symbols),
+                                      _ptr(nsym), nch, block_count, _ptr(state), _stream(stream)), "manchester_decode")
+    return bits
+
+
+def differential_decode(out, bits, nbits, block_num: int, last_bit, stream=None):
+    """differential_decode for every row: bits[nch][>= nbits[ch]] uint8, nbits[nch] int32, last_bit[nch]
+    int32 updated in place; out[nch][>= nbits[ch]] uint8. Rows with nbits <= 0 are left untouched."""
+    nch = bits.shape[0]
+    check(lib().sdr_differential_decode(_ptr(out), _row_stride(out), _ptr(bits), _row_stride(bits), _ptr(nbits), nch,
+                                        block_num, _ptr(last_bit), _stream(stream)), "differential_decode")
+    return out
 
 
 def pll_state_tensor(nch: int, device="cuda", feedbackI=1.0, lastCarrier=1.0):

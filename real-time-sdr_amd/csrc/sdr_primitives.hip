@@ -138,6 +138,10 @@ __global__ void k_manchester(uint8_t* __restrict__ bits, size_t bits_stride, int
     const uint8_t* sy = symbols + (size_t)ch * sym_stride;
     uint8_t* bo = bits + (size_t)ch * bits_stride;
     const int m = nsym[ch];
+    if (m <= 0) {            // an empty row consumes nothing: state and bits row stay (the reference
+        nbits[ch] = 0;       // would read symbols[-1] when a half symbol is pending)
+        return;
+    }
     int half_symbol = state[2 * ch], start = state[2 * ch + 1];
     int nb = 0;
     if (start) bo[nb++] = (uint8_t)half_symbol;
