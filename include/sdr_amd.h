@@ -52,6 +52,8 @@ extern "C" {
                                      * not its sine; not with SDR_FLAG_FAST_FRONTEND (SDR_E_INVALID) */
 #define SDR_FLAG_RDS_QUAD 0x10      /* sdr_rds_post also runs the RDS chain's quadrature branch (below, at
                                      * sdr_ctx_rds_clean_q); mode 0 with rds_on only (SDR_E_INVALID) */
+#define SDR_FLAG_IF_ENVELOPE 0x20   /* the exact front ends also store the IF power row "if_env" (below, at
+                                     * sdr_meter_rf); not with SDR_FLAG_FAST_FRONTEND (SDR_E_INVALID) */
 
 /* ---- phase discriminator (no reference counterpart; sdr_version stays 3, callers detect it by symbol).
  * fmDemodNoArctan's value is Im(x[n] conj(x[n-1])) / |x[n]|^2 = (|x[n-1]| / |x[n]|) sin(dphi): the sine of
@@ -458,6 +460,82 @@ int sdr_meter_rds(sdr_meter *m, sdr_ctx *ctx, void *stream);
 /* host_rows [nch]; synchronises `stream` */
 int sdr_meter_read(sdr_meter *m, sdr_meter_row *host_rows, void *stream);
 int sdr_meter_rows(sdr_meter *m, const sdr_meter_row **dev);   /* the device rows [nch] */
+
+/* ---- reception meter, RF readings (no reference counterpart; sdr_version stays 3, callers detect it by
+ * symbol): the station's level at the antenna and the steadiness of its envelope, which no row behind
+ * the discriminator holds (the discriminator divides the level out).
+ * The row. A context created with SDR_FLAG_IF_ENVELOPE keeps, per block and channel, the IF power
+ *     if_env[c] = fl(fl(I I) + fl(Q Q)),  c = 0 .. block_if - 1
+ * of the decimating FIR's f32 outputs (I, Q) the discriminator reads (rffrontend.cpp:67-68; tuned: the
+ * same FIR behind the mixer): one f32 square each and one f32 sum, each rounded on its own, no FMA.
+ * sdr_frontend, sdr_frontend_tuned and sdr_frontend_pre_parts write it (every c exactly once) next to
+ * fm_demod, with or without SDR_FLAG_PHASE_DEMOD; fm_demod and every other result stay bit for bit what
+ * they are without the flag. It is a parity buffer [2][nch][block_if] like fm_demod, "if_env" of
+ * sdr_ctx_buffer (stride as "fm"); SDR_E_INVALID there on a context without the flag, before the first
+ * front end (also after sdr_ctx_reset), and while the current block is one sdr_push_fm_demod brought (it
+ * brings no I/Q). Without the flag nothing is allocated and the front ends run as they always did.
+ * The reading, over e = the block's if_env row, n = block_if:
+ *   env_sum, env_sq    sum e[i], sum fl(e[i] e[i]), by the meter's summation rule above (256 partials,
+ *                      partial p adding i = p (mod 256) in ascending i from +0, then eight pairing levels)
+ *   env_max, env_min   max e from 0, min e from +infinity; NaN ignored, as for fm_peak (u8 samples and
+ *                      finite taps cannot make one)
+ *   n                  block_if of the block read; flags: SDR_METER_ROW_RF once written; reserved: 0 */
+typedef struct sdr_meter_rf_row {   /* 32 bytes */
+    float env_sum, env_sq, env_min, env_max;
+    int32_t n, flags;
+    int32_t reserved[2];
+} sdr_meter_rf_row;
+#define SDR_METER_ROW_RF 0x4     /* sdr_meter_rf: the whole sdr_meter_rf_row */
+/* device: a second array rf_rows[nch] of the meter handle, all zero after create and sdr_meter_reset.
+ * sdr_meter_rf enqueues one kernel on `stream` (one workgroup of 256 threads per channel, one pass over
+ * the row) that writes every channel's row for `ctx`'s current block with plain stores; it shares no word
+ * with sdr_meter_audio / sdr_meter_rds, so it may run next to them on other contexts and streams. It is
+ * a reader in the parity-release protocol with a slot of its own: the front end of the block two later
+ * waits for it; a context no sdr_meter_rf ran on waits for nothing new. `stream` is the front end's, or
+ * one the caller ordered behind it. SDR_E_INVALID, nothing enqueued: NULL handles, a context of another
+ * nch, mode or device, a context without SDR_FLAG_IF_ENVELOPE, no front end yet, a current block that
+ * sdr_push_fm_demod brought. SDR_E_TIMEOUT as every stage call. */
+int sdr_meter_rf(sdr_meter *m, sdr_ctx *ctx, void *stream);
+/* host_rows [nch]; synchronises `stream` */
+int sdr_meter_rf_read(sdr_meter *m, sdr_meter_rf_row *host_rows, void *stream);
+int sdr_meter_rf_rows(sdr_meter *m, const sdr_meter_rf_row **dev);   /* the device rows [nch] */
+typedef struct sdr_meter_rf_opts { float ripple_max; } sdr_meter_rf_opts;
+void sdr_meter_rf_opts_default(sdr_meter_rf_opts *o);   /* 21.0f / 121.0f */
+#define SDR_METER_RF_WEAK 0x1    /* the row is written and m1 == 0 or ripple > ripple_max */
+typedef struct sdr_meter_rf_state {
+    double level_dbfs, ripple, cnr_db, fade_db, crest_db;
+    int flags;                   /* SDR_METER_RF_WEAK */
+} sdr_meter_rf_state;
+/* One row's readings, host only, in double on the row's values, m1 = env_sum / n, m2 = env_sq / n (both 0
+ * for n <= 0: an unwritten row):
+ *   level_dbfs = 10 log10(m1): 0 dBFS is a carrier of amplitude 1.0 in the front end's (u8 - 128) / 128
+ *                scale, in the passband
+ *   ripple     = (m2 - m1^2) / m1^2, the normalised variance of the IF power: 0 for a constant envelope,
+ *                1 for Gaussian noise alone; 0 when m1 == 0
+ *   cnr_db     the second/fourth-moment estimate for a constant-modulus carrier S in complex Gaussian noise
+ *                N (M2 = S + N, M4 = S^2 + 4 S N + 2 N^2): S = sqrt(max(2 m1^2 - m2, 0)), N = m1 - S,
+ *                cnr_db = 10 log10(S / N); -infinity when S = 0, +infinity when N <= 0 and S > 0
+ *   fade_db    = 10 log10(env_min / m1), crest_db = 10 log10(env_max / m1): the block's deepest null and
+ *                highest peak; both 0 when m1 == 0
+ * The dB of 0 is -infinity. The model gives ripple = (2 r + 1) / (r + 1)^2 at a C/N of r, so the default
+ * ripple_max = 21/121 is r = 10, the textbook FM threshold: derived, not measured.
+ * n makes rows summable: adding env_sum, env_sq and n of several blocks in double and taking the minimum
+ * of env_min and the maximum of env_max gives a run-long row that this function reads as well (the
+ * receiver engine's PREFIX.rfstatus).
+ * Limits. The level is relative to the full scale of the row the front end read; in a wideband run that
+ * is the splitter's output row, and its shift (PREFIX.wide) converts it. cnr_db is a lower bound: whatever
+ * puts AM on the carrier -- multipath, a co-channel, the 100 kHz channel filter acting on a fully deviated
+ * signal -- reads as noise. Measured on the model with the front end's own taps (lpf(2.4e6, 1e5, 101), mode
+ * 0, a carrier of amplitude 0.3 as u8 input, four blocks = 29400 IF samples per figure, tests/rf_model.py):
+ *   - an unmodulated carrier in noise reads within 0.1 dB of its true in-channel C/N from 6 to 22 dB, and
+ *     0.35 to 0.8 dB high from 4 dB down to 0 dB; noise-free it reads 68.6 dB (the u8 rounding);
+ *   - clean, noise-free FM at 75 kHz deviation on a centred carrier caps the estimate at 27.8 dB (1 kHz tone)
+ *     and 22.0 dB (15 kHz tone); with the carrier 20 kHz off centre, where the deviation reaches the filter's
+ *     edge, at 15.3 dB;
+ *   - at 22 dB of true C/N, 75 kHz deviation on a centred carrier reads 1.1 dB (1 kHz tone) and 3.1 dB (15 kHz
+ *     tone) low, 20 kHz off centre 7.6 dB low.
+ * SDR_E_INVALID: NULL arguments, a mode outside 0..3. */
+int sdr_meter_rf_status(int mode, const sdr_meter_rf_row *row, const sdr_meter_rf_opts *o, sdr_meter_rf_state *out);
 
 /* ---- audio finishing (no reference counterpart; sdr_version stays 3, callers detect it by symbol):
  * de-emphasis, a stereo blend driven by the meter's pilot reading, and a gain, over the int16 rows
@@ -928,7 +1006,8 @@ int sdr_get_fm_demod(sdr_ctx *ctx, float *fm, size_t fm_stride, void *stream);
 /* Debug / parity access to intermediates of the current block (device pointers into the
  * context, valid until the next sdr_frontend; "carrier", "stereo_dc" and "ipll" hold whole rows only
  * with SDR_FLAG_KEEP_INTERMEDIATES): name in {"fm","pilot","carrier","band","rds_band",
- * "gen_pilot","ipll","rds_dc","rds_filt","rds_clean","stereo_dc"}; *stride in elements. */
+ * "gen_pilot","ipll","rds_dc","rds_filt","rds_clean","stereo_dc"}; *stride in elements. Flagged rows:
+ * "rds_dc_q", "rds_filt_q", "rds_clean_q" (SDR_FLAG_RDS_QUAD), "if_env" (SDR_FLAG_IF_ENVELOPE, at sdr_meter_rf). */
 int sdr_ctx_buffer(sdr_ctx *ctx, const char *name, const float **ptr, size_t *stride, int *len);
 
 /* ---- RDS quadrature branch (no reference counterpart; callers detect it by symbol). With SDR_FLAG_RDS_QUAD,

@@ -17,7 +17,23 @@
  *                   fm fields are radians) ends every line with
  *                     " peak_khz <v> offset_khz <v>"
  *                   the run's maximum of sdr_meter_deviation's peak and the mean of its offset, in kHz
- *                   of deviation; without that flag the file is byte for byte what it was. */
+ *                   of deviation; without that flag the file is byte for byte what it was.
+ *
+ * The RF readings. A run whose opts->flags hold SDR_FLAG_IF_ENVELOPE and that has a meter (mo != NULL) --
+ * through this or any later entry point that takes mo, tuned, wide, int16 or RDS-decoding runs alike -- is
+ * RF-metered: the RF thread's context alone is created with the flag, and directly behind each block's
+ * sdr_frontend / sdr_frontend_tuned, on the same stream, the RF thread calls sdr_meter_rf on the shared
+ * meter. The flag without a meter, or with SDR_FLAG_FAST_FRONTEND, is SDR_E_INVALID before anything starts.
+ * Every other file of the run is byte for byte that of the run without the flag; with an out_prefix the
+ * run also writes
+ *   PREFIX.rf        per block, nch rows of 32 bytes (sdr_meter_rf_row)
+ *   PREFIX.rfstatus  at the end, one text line per channel:
+ *                      ch <c>: level_dbfs <v> ripple <v> cnr_db <v> fade_db <v> crest_db <v> flags <WEAK|->
+ *                    sdr_meter_rf_status under its default options of the channel's run-long row: env_sum,
+ *                    env_sq and n of its blocks added in double (the sums stored as f32 again), the minimum
+ *                    of env_min and the maximum of env_max. Each <v> is printed with %.3f (an infinity as
+ *                    inf or -inf). In a wide run the level is relative to the full scale of the splitter's
+ *                    output row; the row's shift in PREFIX.wide converts it. */
 #ifndef SDR_MULTI_METER_H
 #define SDR_MULTI_METER_H
 

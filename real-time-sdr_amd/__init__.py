@@ -34,6 +34,7 @@ FLAG_PLL_LIBM = 0x2
 FLAG_KEEP_INTERMEDIATES = 0x4
 PHASE_DEMOD = FLAG_PHASE_DEMOD = 0x8   # fm_demod is the phase step in radians (include/sdr_amd.h); not with FAST
 RDS_QUAD = FLAG_RDS_QUAD = 0x10        # rds / rds_post also run the RDS chain's quadrature branch (Pipeline.rds_clean_q)
+IF_ENVELOPE = FLAG_IF_ENVELOPE = 0x20  # the exact front ends keep the IF power row buffer("if_env") (Meter.rf); not with FAST
 
 _lib = None
 
@@ -78,6 +79,22 @@ class MeterOpts(C.Structure):
 class MeterState(C.Structure):
     """sdr_meter_state: what sdr_meter_status makes of a row."""
     _fields_ = [(n, C.c_double) for n in ("offset", "level_db", "pilot_nr", "rds_nr", "eye_db")] + [("flags", C.c_int)]
+
+
+class MeterRfRow(C.Structure):
+    """sdr_meter_rf_row (include/sdr_amd.h): one channel's IF envelope readings of one block, 32 bytes."""
+    _fields_ = [(n, C.c_float) for n in ("env_sum", "env_sq", "env_min", "env_max")] + \
+               [(n, C.c_int32) for n in ("n", "flags")] + [("reserved", C.c_int32 * 2)]
+
+
+class MeterRfOpts(C.Structure):
+    """sdr_meter_rf_opts: the threshold of meter_rf_status."""
+    _fields_ = [("ripple_max", C.c_float)]
+
+
+class MeterRfState(C.Structure):
+    """sdr_meter_rf_state: what sdr_meter_rf_status makes of a row."""
+    _fields_ = [(n, C.c_double) for n in ("level_dbfs", "ripple", "cnr_db", "fade_db", "crest_db")] + [("flags", C.c_int)]
 
 
 class AudioOpts(C.Structure):
@@ -263,6 +280,11 @@ def lib() -> C.CDLL:
         "sdr_meter_rds": ([vp, vp, vp], i32),
         "sdr_meter_read": ([vp, vp, vp], i32),
         "sdr_meter_rows": ([vp, C.POINTER(vp)], i32),
+        "sdr_meter_rf": ([vp, vp, vp], i32),
+        "sdr_meter_rf_read": ([vp, vp, vp], i32),
+        "sdr_meter_rf_rows": ([vp, C.POINTER(vp)], i32),
+        "sdr_meter_rf_opts_default": ([C.POINTER(MeterRfOpts)], None),
+        "sdr_meter_rf_status": ([i32, C.POINTER(MeterRfRow), C.POINTER(MeterRfOpts), C.POINTER(MeterRfState)], i32),
         "sdr_audio_opts_default": ([C.POINTER(AudioOpts)], None),
         "sdr_audio_coeffs": ([i32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)], i32),
         "sdr_audio_create": ([C.POINTER(vp), i32, i32, i32, i32, C.POINTER(AudioOpts)], i32),
@@ -692,6 +714,36 @@ def meter_deviation(mode: int, rows):
     return out.reshape(rows.shape)
 
 
+def meter_rf_row_dtype():
+    """numpy dtype of sdr_meter_rf_row (32 bytes)."""
+    return _dtype(MeterRfRow)
+
+
+def meter_rf_opts(**opts) -> MeterRfOpts:
+    """The RF status threshold's default (sdr_meter_rf_opts_default) with the given fields replaced."""
+    return _opts(MeterRfOpts, "sdr_meter_rf_opts_default", "meter_rf_status", **opts)
+
+
+def meter_rf_status(mode: int, rows, **opts):
+    """sdr_meter_rf_status of every row (host only): rows is a MeterRfRow or a numpy array of
+    meter_rf_row_dtype() -- a block's, or a run-long one summed as include/sdr_amd.h says; returns a numpy
+    structured array (level_dbfs, ripple, cnr_db, fade_db, crest_db, flags) of the same shape.
+    opts: ripple_max."""
+    import numpy as np
+    o = meter_rf_opts(**opts)
+    if isinstance(rows, MeterRfRow):
+        rows = np.frombuffer(bytes(rows), dtype=meter_rf_row_dtype())[0]
+    rows = np.asarray(rows, dtype=meter_rf_row_dtype())
+    flat = np.ascontiguousarray(rows).reshape(-1)
+    out = np.zeros(flat.shape, np.dtype(MeterRfState))
+    st = MeterRfState()
+    for i in range(flat.size):
+        row = MeterRfRow.from_buffer_copy(flat[i].tobytes())
+        check(lib().sdr_meter_rf_status(mode, C.byref(row), C.byref(o), C.byref(st)), "sdr_meter_rf_status")
+        out[i] = (st.level_dbfs, st.ripple, st.cnr_db, st.fade_db, st.crest_db, st.flags)
+    return out.reshape(rows.shape)
+
+
 class Meter(_Handle):
     """The reception meter of `nch` channels of one mode (sdr_meter_*): per block audio(pipe, lr) after
     the block's stereo stage and rds(pipe) after its RDS stage -- on one Pipeline or on two joined by
@@ -714,6 +766,33 @@ class Meter(_Handle):
     def rds(self, pipe: "Pipeline", stream=None):
         """rds_sq and the eye fields of pipe's current block (after rds() / rds_post())."""
         check(lib().sdr_meter_rds(self._h, pipe._h, _stream(stream)), "sdr_meter_rds")
+
+    def rf(self, pipe: "Pipeline", stream=None):
+        """The IF envelope readings of pipe's current block (an IF_ENVELOPE pipeline, after its front end), into
+        rows of their own. Enqueues, no sync."""
+        check(lib().sdr_meter_rf(self._h, pipe._h, _stream(stream)), "sdr_meter_rf")
+
+    def read_rf(self, stream=None):
+        """numpy structured array [nch] of meter_rf_row_dtype(); synchronises the stream."""
+        return self._records("sdr_meter_rf_read", meter_rf_row_dtype(), stream)
+
+    def rf_rows(self) -> int:
+        """Device address of the RF rows [nch] (sdr_meter_rf_rows)."""
+        p = C.c_void_p()
+        check(lib().sdr_meter_rf_rows(self._h, C.byref(p)), "sdr_meter_rf_rows")
+        return int(p.value)
+
+    def rf_rows_into(self, out, stream=None):
+        """The RF rows copied on the device into `out` (a contiguous uint8 tensor of nch * 32 bytes) in `stream`'s
+        order, without synchronising (as rows_into)."""
+        nbytes = self.nch * C.sizeof(MeterRfRow)
+        if out.numel() * out.element_size() != nbytes or not out.is_contiguous():
+            raise SdrError(f"Meter.rf_rows_into: expected a contiguous tensor of {nbytes} bytes", -1)
+        rc = _hip().hipMemcpyAsync(C.c_void_p(out.data_ptr()), C.c_void_p(self.rf_rows()), C.c_size_t(nbytes),
+                                   C.c_int(3), C.c_void_p(_stream(stream)))
+        if rc != 0:
+            raise SdrError(f"hipMemcpyAsync failed ({rc})")
+        return out
 
     def rows(self, stream=None):
         """numpy structured array [nch] of meter_row_dtype(); synchronises the stream."""
@@ -1227,6 +1306,7 @@ class Pipeline(_Handle):
         check(lib().sdr_ctx_info(self._h, C.byref(info)), "sdr_ctx_info")
         self.info = info
         self.nch = nch
+        self.flags = flags
         i32 = torch.int32
         dev = self.torch_device
         self.offset = torch.zeros(nch, dtype=i32, device=dev)

@@ -136,6 +136,7 @@ int init_state(sdr_ctx* c, hipStream_t s) {
     c->block = -1;
     c->stereo_done = c->rds_dsp_done = c->rds_bits_done = c->mono_done = -1;
     c->st_pre_done = c->st_pll_done = c->rds_pre_done = c->rds_pll_done = -1;
+    c->env_block = -1;             // (if_env itself needs no clearing: every element is written before it is valid)
     (void)in;
     return SDR_OK;
 }
@@ -213,6 +214,7 @@ FrontendArgs frontend_args(const sdr_ctx* c, const uint8_t* iq, size_t iq_stride
     a.fm = c->fm + p * c->fm_par;
     a.fm_other = c->fm + (p ^ 1) * c->fm_par;
     a.fm_stride = c->fm_stride;
+    a.env = c->if_env ? c->if_env + p * c->fm_par : nullptr;
     a.nch = c->nch;
     a.ntaps = c->ntaps;
     a.block_iq = in.block_iq;
@@ -241,7 +243,8 @@ FrontendArgs frontend_args(const sdr_ctx* c, const uint8_t* iq, size_t iq_stride
 // The reception meter's calls are readers too (sdr_meter.hip): REL_METER_A sdr_meter_audio (fm, pilot),
 // REL_METER_R sdr_meter_rds (rband) -- a slot each, because the two may run on different streams and a
 // slot's word is stored, not added to. On a context no meter call ran on their counts stay 0 and
-// release_wait skips them: such a context enqueues what it always did.
+// release_wait skips them: such a context enqueues what it always did. REL_METER_RF sdr_meter_rf (if_env) is the
+// third such reader, with a slot of its own for the same reason; only the front ends overwrite its row.
 int release_record(sdr_ctx* c, unsigned slot, hipStream_t s) {
     sdr_ctx::Rel& r = c->rel;
     const int p = c->parity, k = __builtin_ctz(slot);
@@ -291,6 +294,8 @@ int sdr_ctx_create(sdr_ctx** out, int device, int nch, int mode, int rds_on, int
     *out = nullptr;
     if ((flags & SDR_FLAG_FAST_FRONTEND) && (flags & SDR_FLAG_PHASE_DEMOD))
         return fail(SDR_E_INVALID, "SDR_FLAG_PHASE_DEMOD needs the exact front end (not SDR_FLAG_FAST_FRONTEND)");
+    if ((flags & SDR_FLAG_FAST_FRONTEND) && (flags & SDR_FLAG_IF_ENVELOPE))
+        return fail(SDR_E_INVALID, "SDR_FLAG_IF_ENVELOPE needs the exact front end (not SDR_FLAG_FAST_FRONTEND)");
     if ((flags & SDR_FLAG_RDS_QUAD) && !(rds_on && sdr_rds_mode_ok(mode)))
         return fail(SDR_E_INVALID, "SDR_FLAG_RDS_QUAD needs rds_on and mode 0 (mode %d, rds_on %d)", mode, rds_on);
     int ndev = 0;
@@ -431,6 +436,7 @@ int sdr_ctx_create(sdr_ctx** out, int device, int nch, int mode, int rds_on, int
         TRY(dalloc(c, &base, 2 * c->fm_par)); c->rdc_q = base + HIST;
         TRY(dalloc(c, &base, 2 * c->rf_par)); c->rfilt_q = base + HIST;
     }
+    if (flags & SDR_FLAG_IF_ENVELOPE) TRY(dalloc(c, &c->if_env, 2 * c->fm_par));
     c->plain_stride = round_up((size_t)in.block_if, 64);
     c->pll_stride = round_up((size_t)in.block_if + 1, 64);
     c->clean_stride = round_up((size_t)in.n_rds, 64);
@@ -533,6 +539,16 @@ int sdr_ctx_buffer(sdr_ctx* c, const char* name, const float** ptr, size_t* stri
     if (!c || !name || !ptr || !stride || !len) return fail(SDR_E_INVALID, "null argument");
     const sdr_info& in = c->info;
     const int p = c->parity;
+    if (std::strcmp(name, "if_env") == 0) {
+        // SDR_FLAG_IF_ENVELOPE: the current block's IF power row, if a front end wrote one for it
+        if (!c->if_env) return fail(SDR_E_INVALID, "buffer if_env needs SDR_FLAG_IF_ENVELOPE");
+        if (c->block < 0 || c->env_block != c->block)
+            return fail(SDR_E_INVALID, "buffer if_env: the current block has none (no front end yet, or sdr_push_fm_demod)");
+        *ptr = c->if_env + p * c->fm_par;
+        *stride = c->fm_stride;
+        *len = in.block_if;
+        return SDR_OK;
+    }
     struct E { const char* n; const float* p; size_t s; int l; } tab[] = {
         {"fm", c->fm_cur(), c->fm_stride, in.block_if},
         {"pilot", c->plain(c->pilot), c->plain_stride, in.block_if},

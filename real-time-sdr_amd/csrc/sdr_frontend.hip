@@ -32,12 +32,14 @@ namespace {
 //        prev = last decimated (I, Q) of the previous block. Both double-buffered by parity.
 // ------------------------------------------------------------------------------------------
 // PH: the phase discriminator (SDR_FLAG_PHASE_DEMOD, demod_phase.h) instead of demod.cpp:8-19.
-template <bool PH>
+// ENV: the IF envelope row too (SDR_FLAG_IF_ENVELOPE): env[n] = fl(fl(I I) + fl(Q Q)) of every output n
+// the tile writes (env: this parity's rows, channel stride fm_stride).
+template <bool PH, bool ENV>
 __global__ __launch_bounds__(BLK) void k_frontend(
     const uint8_t* __restrict__ iq, size_t iq_stride, const uint8_t* __restrict__ tail_in,
     uint8_t* __restrict__ tail_out, const float2* __restrict__ prev_in, float2* __restrict__ prev_out,
     const float* __restrict__ h, int ntaps, int D, int block_iq, int block_if, int tile,
-    float* __restrict__ fm, const float* __restrict__ fm_other, size_t fm_stride) {
+    float* __restrict__ fm, const float* __restrict__ fm_other, size_t fm_stride, float* __restrict__ env) {
     extern __shared__ float4 smem4[];
     const int ntaps_pad = (ntaps + 3) & ~3;
     float* sh = reinterpret_cast<float*>(smem4);
@@ -92,6 +94,7 @@ __global__ __launch_bounds__(BLK) void k_frontend(
             r = (float)((double)num / den);
         }
         out[n] = r;
+        if constexpr (ENV) env[(size_t)ch * fm_stride + n] = cur.x * cur.x + cur.y * cur.y;
     }
     if (n1 == block_if && tid == 0) prev_out[ch] = sds[n1 - 1 - c0];
     if (blockIdx.x == 0) {
@@ -431,9 +434,13 @@ __device__ __forceinline__ void fe_fir(const uint8_t* __restrict__ sw, const flo
 // (fm_demod of the channel; c0 is the tile's carry output, never written); the block's last (I, Q)
 // goes to prev_out. PH: the phase discriminator (SDR_FLAG_PHASE_DEMOD, demod_phase.h) instead -- all
 // f32, two outputs per packed polynomial, none of the f64 reciprocal, tie key or division fallback.
-template <int R, bool PH>
+// ENV: the IF envelope row too (SDR_FLAG_IF_ENVELOPE): env[c] = fl(fl(I I) + fl(Q Q)) of every output c
+// whose fm sample is stored, by the same rule and with the same aligned float2 fast path (env: the
+// channel's row, laid out as out is; unused without ENV).
+template <int R, bool PH, bool ENV>
 __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int ch, const float2* __restrict__ prev_in,
-                                              float2* __restrict__ prev_out, float* __restrict__ out, int block_if) {
+                                              float2* __restrict__ prev_out, float* __restrict__ out,
+                                              float* __restrict__ env, int block_if) {
     // ---- discriminator (demod.cpp:8-19); the previous output of lane t's first comes from t-1
     const f32x2 left = f32x2{__shfl_up(acc[R - 1].x, 1), __shfl_up(acc[R - 1].y, 1)};
     const int t = threadIdx.x;
@@ -507,6 +514,12 @@ __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int
     }
     }                                                // if constexpr (PH) .. else
 #endif
+    float e[ENV ? R : 1];                            // the IF power of each output: a square each, one sum
+    (void)e;
+    if constexpr (ENV) {
+#pragma unroll
+        for (int r = 0; r < R; r++) e[r] = acc[r].x * acc[r].x + acc[r].y * acc[r].y;
+    }
     if (t > 0 && cbase + R < block_if) {             // all R outputs written, none the block's last
         if ((reinterpret_cast<uintptr_t>(out + cbase) & 7) == 0) {
 #pragma unroll
@@ -515,11 +528,23 @@ __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int
 #pragma unroll
             for (int r = 0; r < R; r++) out[cbase + r] = v[r];
         }
+        if constexpr (ENV) {
+            if ((reinterpret_cast<uintptr_t>(env + cbase) & 7) == 0) {
+#pragma unroll
+                for (int r = 0; r < R; r += 2) *reinterpret_cast<float2*>(env + cbase + r) = make_float2(e[r], e[r + 1]);
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; r++) env[cbase + r] = e[r];
+            }
+        }
     } else {
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int c = cbase + r;
-            if (c > c0 && c >= 0 && c < block_if) out[c] = v[r];
+            if (c > c0 && c >= 0 && c < block_if) {
+                out[c] = v[r];
+                if constexpr (ENV) env[c] = e[r];
+            }
             if (c == block_if - 1) prev_out[ch] = make_float2(acc[r].x, acc[r].y);
         }
     }
@@ -532,13 +557,13 @@ __device__ __forceinline__ void fe_disc_store(const f32x2 (&acc)[R], int c0, int
 // last runs into the padding, u8 128 = 0.0f) stage per dword from the block, the tail or the pad.
 // Tiles j0 .. j0+jn-1 of every channel (blockIdx.x = ch*jn + j - j0): the whole block (j0 = 0, jn =
 // tiles per channel) or one part of it (sdr_frontend_pre_parts, the pipeline fill).
-template <int R, int D, bool PH>
+template <int R, int D, bool PH, bool ENV>
 __global__ __launch_bounds__(64) void k_frontend2(
     const uint8_t* __restrict__ iq, size_t iq_stride, const uint8_t* __restrict__ tail_in,
     uint8_t* __restrict__ tail_out, const float2* __restrict__ prev_in, float2* __restrict__ prev_out,
     const float* __restrict__ hs, int block_iq, int block_if,
     float* __restrict__ fm, const float* __restrict__ fm_other, size_t fm_stride, int j0, int jn,
-    const uint32_t* __restrict__ pad, unsigned long long* __restrict__ stamps) {
+    const uint32_t* __restrict__ pad, unsigned long long* __restrict__ stamps, float* __restrict__ env) {
     constexpr int NT = 101, HP = NT - 1, NTH = 64;
     // sdr_frontend_timing: this workgroup's start and end on the 100 MHz clock (the launch's span is
     // the earliest start to the latest end, computed on the host)
@@ -614,7 +639,8 @@ __global__ __launch_bounds__(64) void k_frontend2(
     __syncthreads();
     f32x2 acc[R];
     fe_fir<R, D>(sw, hs, acc);
-    fe_disc_store<R, PH>(acc, c0, ch, prev_in, prev_out, fm + (size_t)ch * fm_stride, block_if);
+    fe_disc_store<R, PH, ENV>(acc, c0, ch, prev_in, prev_out, fm + (size_t)ch * fm_stride,
+                              ENV ? env + (size_t)ch * fm_stride : nullptr, block_if);
     float* out = fm + (size_t)ch * fm_stride;
     if (j == 0) {
         const uint16_t* last = reinterpret_cast<const uint16_t*>(src) + (block_iq - HP);
@@ -719,13 +745,14 @@ __device__ __forceinline__ void tn_fir(const float* __restrict__ sy, const float
 }
 
 // tune[pos] = {channel, source row, khz mod N, 1: this channel stores its row's tail}
-template <int R, int D, bool PH>
+template <int R, int D, bool PH, bool ENV>
 __global__ __launch_bounds__(64) void k_frontend_tuned(
     const uint8_t* __restrict__ iq, size_t iq_stride, const uint8_t* __restrict__ tail_in,
     uint8_t* __restrict__ tail_out, const float2* __restrict__ prev_in, float2* __restrict__ prev_out,
     const float* __restrict__ hs, const float* __restrict__ qtab, const int4* __restrict__ tune, int phase0,
     int block_iq, int block_if, float* __restrict__ fm, const float* __restrict__ fm_other, size_t fm_stride,
-    int tiles, int total, int per, int nxcc, const uint32_t* __restrict__ pad, unsigned long long* __restrict__ stamps) {
+    int tiles, int total, int per, int nxcc, const uint32_t* __restrict__ pad, unsigned long long* __restrict__ stamps,
+    float* __restrict__ env) {
     constexpr int NT = 101, HP = NT - 1, NTH = 64;
     constexpr int N = tn_n(D), Q4 = N / 4;
     if (stamps && threadIdx.x == 0) stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -822,7 +849,7 @@ __global__ __launch_bounds__(64) void k_frontend_tuned(
     f32x2 acc[R];
     tn_fir<R, D>(reinterpret_cast<const float*>(sy4), hs, acc);
     float* out = fm + (size_t)ch * fm_stride;
-    fe_disc_store<R, PH>(acc, c0, ch, prev_in, prev_out, out, block_if);
+    fe_disc_store<R, PH, ENV>(acc, c0, ch, prev_in, prev_out, out, ENV ? env + (size_t)ch * fm_stride : nullptr, block_if);
     if (j == 0) {
         if (tn.w) {                                   // one channel per source row keeps the row's tail
             const uint16_t* last = reinterpret_cast<const uint16_t*>(src) + (block_iq - HP);
@@ -869,10 +896,12 @@ int frontend_launch(const FrontendArgs& a, hipStream_t s, int j0, int jn) {
     // (a.stamps); the generic kernel records HIP events with the launch (hipExtLaunchKernelGGL: the
     // start event is a marker ahead of the dispatch, so its span exceeds the kernel's by the marker's
     // latency, ~9 us)
-#define FE2(DD, PP)                                                                                           \
-    hipExtLaunchKernelGGL((k_frontend2<FE_R, DD, PP>), g2, dim3(64), 0, s, a.ev0, a.ev1, 0, iq, iq_stride, tail_in, \
+    // a.env (SDR_FLAG_IF_ENVELOPE) picks the instantiations that also store the IF envelope row
+#define FE2E(DD, PP, EE)                                                                                      \
+    hipExtLaunchKernelGGL((k_frontend2<FE_R, DD, PP, EE>), g2, dim3(64), 0, s, a.ev0, a.ev1, 0, iq, iq_stride, tail_in, \
                           tail_out, prev_in, prev_out, a.hs, a.block_iq, a.block_if, fm_p, fm_o, a.fm_stride, j0, jn, \
-                          a.pad80, a.stamps)
+                          a.pad80, a.stamps, a.env)
+#define FE2(DD, PP) do { if (a.env) FE2E(DD, PP, true); else FE2E(DD, PP, false); } while (0)
     if (a.fast) {
         if (j0 != 0 || jn != tiles_ch) return fail(SDR_E_INVALID, "frontend: parts need the exact front end");
         const v4i* af = static_cast<const v4i*>(a.afrag);
@@ -899,14 +928,16 @@ int frontend_launch(const FrontendArgs& a, hipStream_t s, int j0, int jn) {
         const int tile = FIR_TILE;
         dim3 grid(cdiv(a.block_if, tile), a.nch);
         const size_t lds = frontend_lds_bytes(a.ntaps, tile, a.D);
-#define FEG(PP)                                                                                               \
-        hipExtLaunchKernelGGL(k_frontend<PP>, grid, dim3(BLK), (uint32_t)lds, s, a.ev0, a.ev1, 0, iq, iq_stride,     \
+#define FEG(PP, EE)                                                                                           \
+        hipExtLaunchKernelGGL((k_frontend<PP, EE>), grid, dim3(BLK), (uint32_t)lds, s, a.ev0, a.ev1, 0, iq, iq_stride, \
                               tail_in, tail_out, prev_in, prev_out, a.h, a.ntaps, a.D, a.block_iq, a.block_if, tile,   \
-                              fm_p, fm_o, a.fm_stride)
-        if (a.phase) FEG(true); else FEG(false);
+                              fm_p, fm_o, a.fm_stride, a.env)
+        if (a.env) { if (a.phase) FEG(true, true); else FEG(false, true); }
+        else { if (a.phase) FEG(true, false); else FEG(false, false); }
 #undef FEG
     }
 #undef FE2
+#undef FE2E
     LAUNCH_CHECK();
     return SDR_OK;
 }
@@ -929,14 +960,16 @@ int frontend_tuned_launch(const FrontendArgs& a, const float* ht, const float* q
     const int tiles = tuned_tiles(a.block_if), total = tiles * a.nch, per = cdiv(total, nxcc);
     const dim3 g(per * nxcc);
     const int4* tn = reinterpret_cast<const int4*>(tune);
-#define FET(DD, PP)                                                                                               \
-    hipLaunchKernelGGL((k_frontend_tuned<TN_R, DD, PP>), g, dim3(64), 0, s, a.iq, a.iq_stride, a.tail_in, a.tail_out,    \
+#define FETE(DD, PP, EE)                                                                                          \
+    hipLaunchKernelGGL((k_frontend_tuned<TN_R, DD, PP, EE>), g, dim3(64), 0, s, a.iq, a.iq_stride, a.tail_in, a.tail_out, \
                        a.prev_in, a.prev_out, ht, qtab, tn, phase0, a.block_iq, a.block_if, a.fm, a.fm_other,         \
-                       a.fm_stride, tiles, total, per, nxcc, a.pad80, a.stamps)
+                       a.fm_stride, tiles, total, per, nxcc, a.pad80, a.stamps, a.env)
+#define FET(DD, PP) do { if (a.env) FETE(DD, PP, true); else FETE(DD, PP, false); } while (0)
     if (a.D == 10) { if (a.phase) FET(10, true); else FET(10, false); }
     else if (a.D == 4) { if (a.phase) FET(4, true); else FET(4, false); }
     else { if (a.phase) FET(3, true); else FET(3, false); }
 #undef FET
+#undef FETE
     LAUNCH_CHECK();
     return SDR_OK;
 }

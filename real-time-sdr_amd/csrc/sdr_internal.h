@@ -111,6 +111,7 @@ struct FrontendArgs {
     float* fm;                 // this parity's fm_demod stream (data base)
     const float* fm_other;     // the other parity's (history source)
     size_t fm_stride;
+    float* env;                // SDR_FLAG_IF_ENVELOPE: this parity's if_env rows (stride fm_stride), else null
     int nch, ntaps, block_iq, block_if, D;
     const float* h;            // plain taps (generic kernel)
     const float* hs;           // register-blocked tap table (k_frontend2)
@@ -216,8 +217,9 @@ FrontendArgs frontend_args(const sdr_ctx* c, const uint8_t* iq, size_t iq_stride
 PllJob stereo_job(sdr_ctx* c);   // stereo.cpp:77: fmpll(pilot, 19e3, rf_Fs/rf_decim, ..., 2.0, 0, 0.01)
 PllJob rds_job(sdr_ctx* c);      // rds.cpp:119: fmpll(gen_pilot, 114e3, if_Fs, ..., 0.5, 0, 0.001)
 // parity release (sdr_ctx::Rel): the slots' readers, as bits of a wait's slot set
-constexpr unsigned REL_MONO = 1u, REL_STEREO = 2u, REL_RDS = 4u, REL_METER_A = 8u, REL_METER_R = 16u;
-constexpr unsigned REL_ALL = REL_MONO | REL_STEREO | REL_RDS | REL_METER_A | REL_METER_R;
+constexpr unsigned REL_MONO = 1u, REL_STEREO = 2u, REL_RDS = 4u, REL_METER_A = 8u, REL_METER_R = 16u,
+                   REL_METER_RF = 32u;
+constexpr unsigned REL_ALL = REL_MONO | REL_STEREO | REL_RDS | REL_METER_A | REL_METER_R | REL_METER_RF;
 // the reader `slot` (one REL_ bit) has read the current block's parity buffers on s
 int release_record(sdr_ctx* c, unsigned slot, hipStream_t s);
 // s waits until the readers `slots` of parity p have released the last block they read
@@ -256,6 +258,7 @@ struct sdr_meter {
     int device = 0, nch = 0, mode = 0;
     float* h = nullptr;             // the noise band-pass taps (device)
     sdr_meter_row* rows = nullptr;  // [nch] (device)
+    sdr_meter_rf_row* rf_rows = nullptr;   // [nch] (device): sdr_meter_rf's rows
 };
 
 struct sdr_ctx {
@@ -279,6 +282,11 @@ struct sdr_ctx {
     // SDR_FLAG_RDS_QUAD (allocated only with it): the quadrature branch's extended streams, laid out as rdc and
     // rfilt are, its output rows, and ipll_q[n] of the last block of each parity, [2][nch]
     float *rdc_q = nullptr, *rfilt_q = nullptr, *rds_clean_q = nullptr, *ipll_q_last = nullptr;
+    // SDR_FLAG_IF_ENVELOPE (allocated only with it): the IF power rows [2][nch][fm_stride] the exact front ends
+    // write next to fm (parity 0's base; no history), and the block they were last written for (a block that
+    // sdr_push_fm_demod brought has none)
+    float* if_env = nullptr;
+    long long env_block = -1;
     int* rds_ptq = nullptr;                             // RDS resampler (q << 8 | phase) per output
     bool rdsbb_all101 = false;                          // every RDS polyphase row has 101 taps
     bool audio_u1_101 = false;                          // audio resampler U == 1 with 101 taps
@@ -341,11 +349,11 @@ struct sdr_ctx {
     // 2 sdr_rds_post's mixer (rband, t_rds, ipll), stored on the reader's stream (stream) after
     // its kernels; the producers of the block two later wait for the count on their own streams.
     // Slots 3 and 4 are the reception meter's two calls (sdr_meter.hip), which may run on two streams:
-    // 3 sdr_meter_audio (fm, pilot), 4 sdr_meter_rds (rband); their counts stay 0, and nothing waits
-    // for them, on a context no meter call ran on
+    // 3 sdr_meter_audio (fm, pilot), 4 sdr_meter_rds (rband), 5 sdr_meter_rf (if_env, which only the front
+    // ends write); their counts stay 0, and nothing waits for them, on a context no meter call ran on
     // The release functions of sdr_ctx.hip own it; the output stages read fail_words (block_poison).
     struct Rel {
-        static constexpr int SLOTS = 5;
+        static constexpr int SLOTS = 6;
         uint32_t* words = nullptr;                      // [2][SLOTS] counters
         uint32_t seq[2][SLOTS] = {};
         hipStream_t stream[2][SLOTS] = {};

@@ -1255,6 +1255,7 @@ int sdr_frontend(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* stream) 
     if (timed) ft.n++;
     c->parity = p;
     c->block++;
+    if (a.env) c->env_block = c->block;
     return SDR_OK;
 }
 
@@ -1336,6 +1337,7 @@ int sdr_frontend_tuned(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, void* st
     if (timed) ft.n++;
     c->parity = p;
     c->block++;
+    if (a.env) c->env_block = c->block;
     return SDR_OK;
 }
 
@@ -1677,6 +1679,7 @@ int sdr_frontend_pre_parts(sdr_ctx* c, const uint8_t* iq, size_t iq_stride, int 
         if (r) return undo(r);
     }
     c->st_pre_done = c->rds_pre_done = c->block;
+    if (a.env) c->env_block = c->block;   // (every front-end tile ran: the row is whole)
     return sdr_plls_signal(c, stream);   // the whole block: the launch's flag
 }
 

@@ -3,13 +3,15 @@
 // audio peak and power), reduced from rows the pipeline already keeps in HBM, and the host-side
 // arithmetic that turns a row into ratios and flags. No reference counterpart.
 //
-// Two kernels, one launch per call, one workgroup of 256 threads per channel:
+// Three kernels, one launch per call, one workgroup of 256 threads per channel:
 //   k_meter_audio   fm (with its 100 history samples) is staged once in LDS and serves the fm sums and
 //                   the noise FIR; the FIR (101 taps, every fifth output, the reference's convolveFIR
 //                   order, filter.cpp:106-121) is fused with its square-and-sum, y is never stored;
 //                   the pilot row and the int16 L/R row are read once from HBM.
 //   k_meter_rds     the rds_band row is read once; rds_clean is staged in LDS for cdr()
 //                   (rds_utilities.cpp:4-21) and the eye samples at the offset it returns.
+//   k_meter_rf      the IF power row the front ends keep with SDR_FLAG_IF_ENVELOPE is read once: its sum,
+//                   its sum of squares, its minimum and maximum, into a row array of its own.
 //
 // Summation order (a numpy model reproduces every float bit for bit; no FMA, each product and sum
 // rounded on its own): a float sum over a row of length m has 256 partials, partial p adding the
@@ -66,6 +68,11 @@ __device__ __forceinline__ void pair_block(float (&v)[NV], float (*red)[MT]) {
 __device__ __forceinline__ float max_wave(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ float min_wave(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
     return v;
 }
 __device__ __forceinline__ int max_wave(int v) {
@@ -246,6 +253,54 @@ __global__ __launch_bounds__(MT) void k_meter_rds(const MeterRds a) {
     }
 }
 
+struct MeterRf {
+    const float* env;       // this parity's if_env rows
+    size_t stride;
+    int n;
+    sdr_meter_rf_row* rows;
+};
+
+// A row of its own per channel, written whole by thread 0 with plain stores: no word shared with the
+// other two calls.
+__global__ __launch_bounds__(MT) void k_meter_rf(const MeterRf a) {
+    __shared__ float red[2][MT];
+    __shared__ float wmn[MT / 64], wmx[MT / 64];
+    const int ch = blockIdx.x, p = threadIdx.x, wave = p >> 6;
+    const float* __restrict__ e = a.env + (size_t)ch * a.stride;
+    float s = 0.0f, q = 0.0f, mx = 0.0f, mn = __builtin_inff();
+#pragma unroll 8
+    for (int i = p; i < a.n; i += MT) {
+        const float v = e[i];
+        s = s + v;
+        q = q + v * v;
+        mx = fmaxf(mx, v);          // (both ignore NaN)
+        mn = fminf(mn, v);
+    }
+    float sums[2] = {s, q};
+    pair_block(sums, red);
+    mx = max_wave(mx);
+    mn = min_wave(mn);
+    if ((p & 63) == 0) {
+        wmx[wave] = mx;
+        wmn[wave] = mn;
+    }
+    __syncthreads();
+    if (p == 0) {
+        for (int w = 1; w < MT / 64; w++) {
+            mx = fmaxf(mx, wmx[w]);
+            mn = fminf(mn, wmn[w]);
+        }
+        sdr_meter_rf_row* row = a.rows + ch;
+        row->env_sum = sums[0];
+        row->env_sq = sums[1];
+        row->env_min = mn;
+        row->env_max = mx;
+        row->n = a.n;
+        row->flags = SDR_METER_ROW_RF;
+        row->reserved[0] = row->reserved[1] = 0;
+    }
+}
+
 // num / den of two mean powers: 0 for a zero numerator, +inf for a zero denominator under a positive one
 double ratio(double num, double den) {
     if (!(num != 0.0)) return 0.0;
@@ -304,6 +359,32 @@ int sdr_meter_status(int mode, const sdr_meter_row* row, const sdr_meter_opts* o
     return SDR_OK;
 }
 
+void sdr_meter_rf_opts_default(sdr_meter_rf_opts* o) {
+    if (!o) return;
+    o->ripple_max = 21.0f / 121.0f;
+}
+
+int sdr_meter_rf_status(int mode, const sdr_meter_rf_row* row, const sdr_meter_rf_opts* o, sdr_meter_rf_state* out) {
+    sdr_info in;
+    if (const int r = mode_info(&in, 1, mode, 1)) return r;
+    if (!row || !o || !out) return fail(SDR_E_INVALID, "meter_rf_status: null argument");
+    const double n = row->n;
+    const double m1 = row->n > 0 ? (double)row->env_sum / n : 0.0, m2 = row->n > 0 ? (double)row->env_sq / n : 0.0;
+    const bool zero = !(m1 != 0.0);
+    out->level_dbfs = 10.0 * std::log10(m1);
+    out->ripple = zero ? 0.0 : (m2 - m1 * m1) / (m1 * m1);
+    const double S = std::sqrt(std::max(2.0 * m1 * m1 - m2, 0.0)), N = m1 - S;
+    if (!(S > 0.0)) out->cnr_db = -HUGE_VAL;
+    else if (N <= 0.0) out->cnr_db = HUGE_VAL;
+    else out->cnr_db = 10.0 * std::log10(S / N);
+    out->fade_db = zero ? 0.0 : 10.0 * std::log10((double)row->env_min / m1);
+    out->crest_db = zero ? 0.0 : 10.0 * std::log10((double)row->env_max / m1);
+    int f = 0;
+    if ((row->flags & SDR_METER_ROW_RF) && (zero || out->ripple > (double)o->ripple_max)) f |= SDR_METER_RF_WEAK;
+    out->flags = f;
+    return SDR_OK;
+}
+
 int sdr_meter_deviation(int mode, const sdr_meter_row* row, double* peak_khz, double* rms_khz, double* offset_khz) {
     sdr_info in;
     if (const int r = mode_info(&in, 1, mode, 1)) return r;
@@ -331,24 +412,27 @@ int sdr_meter_create(sdr_meter** out, int device, int nch, int mode) {
     hipError_t e = hipSuccess;
     dev_alloc(e, &m->h, sizeof(h));
     dev_alloc(e, &m->rows, (size_t)nch * sizeof(sdr_meter_row));
+    dev_alloc(e, &m->rf_rows, (size_t)nch * sizeof(sdr_meter_rf_row));
     if (e == hipSuccess) e = hipMemcpy(m->h, h, sizeof(h), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(m->rows, 0, (size_t)nch * sizeof(sdr_meter_row));
+    if (e == hipSuccess) e = hipMemset(m->rf_rows, 0, (size_t)nch * sizeof(sdr_meter_rf_row));
     return create_done(e, m, out, sdr_meter_destroy, "meter_create");
 }
 
 int sdr_meter_destroy(sdr_meter* m) {
     if (!m) return fail(SDR_E_INVALID, "meter_destroy: null meter");
-    return destroy_handle(m, {m->h, m->rows});
+    return destroy_handle(m, {m->h, m->rows, m->rf_rows});
 }
 
 int sdr_meter_reset(sdr_meter* m, void* stream) {
     if (!m) return fail(SDR_E_INVALID, "meter_reset: null meter");
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipMemsetAsync(m->rows, 0, (size_t)m->nch * sizeof(sdr_meter_row), (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(m->rf_rows, 0, (size_t)m->nch * sizeof(sdr_meter_rf_row), (hipStream_t)stream));
     return SDR_OK;
 }
 
-// the checks both calls share: handles, the context's state, the same shape and device
+// the checks the calls share: handles, the context's state, the same shape and device
 static int meter_check(const sdr_meter* m, const sdr_ctx* c, const char* what) {
     if (!m || !c) return fail(SDR_E_INVALID, "%s: null handle", what);
     if (const int rf = check_failed(c, what)) return rf;
@@ -403,6 +487,36 @@ int sdr_meter_rds(sdr_meter* m, sdr_ctx* c, void* stream) {
     hipLaunchKernelGGL(k_meter_rds, dim3(m->nch), dim3(MT), (size_t)in.n_rds * sizeof(float), s, a);
     LAUNCH_CHECK();
     return release_record(c, REL_METER_R, s);   // rds_band of this parity read
+}
+
+int sdr_meter_rf(sdr_meter* m, sdr_ctx* c, void* stream) {
+    if (const int r = meter_check(m, c, "meter_rf")) return r;
+    if (!c->if_env) return fail(SDR_E_INVALID, "meter_rf: the context has no IF envelope row (SDR_FLAG_IF_ENVELOPE)");
+    if (c->block < 0 || c->env_block != c->block)
+        return fail(SDR_E_INVALID, "meter_rf: the current block has no IF envelope row (no front end yet, or "
+                                   "sdr_push_fm_demod brought it)");
+    HIP_TRY(hipSetDevice(m->device));
+    MeterRf a{};
+    a.env = c->if_env + c->parity * c->fm_par;
+    a.stride = c->fm_stride;
+    a.n = c->info.block_if;
+    a.rows = m->rf_rows;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_meter_rf, dim3(m->nch), dim3(MT), 0, s, a);
+    LAUNCH_CHECK();
+    return release_record(c, REL_METER_RF, s);   // if_env of this parity read
+}
+
+int sdr_meter_rf_read(sdr_meter* m, sdr_meter_rf_row* host_rows, void* stream) {
+    if (!m || !host_rows) return fail(SDR_E_INVALID, "meter_rf_read: null argument");
+    HIP_TRY(hipSetDevice(m->device));
+    return copy_records(m->rf_rows, host_rows, m->nch, S(stream));
+}
+
+int sdr_meter_rf_rows(sdr_meter* m, const sdr_meter_rf_row** dev) {
+    if (!m || !dev) return fail(SDR_E_INVALID, "meter_rf_rows: null argument");
+    *dev = m->rf_rows;
+    return SDR_OK;
 }
 
 int sdr_meter_read(sdr_meter* m, sdr_meter_row* host_rows, void* stream) {

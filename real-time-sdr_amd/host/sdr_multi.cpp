@@ -1,7 +1,7 @@
 // sdr_multi.cpp -- multi-channel receiver CLI over the engine of include/sdr_multi.h (the reference
 // program's three stage threads over nch channels, project.cpp:134-136).
 //
-//   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter]
+//   sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] [--tune FILE] [--meter [--rf]]
 //             [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L] [--rds-carrier ref|quad]]
 //   sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] [--step K] [--thr DB]
 //   sdr_multi NCH --wide W [--shift S] --tune FILE ...          (the receiver on wide captures)
@@ -22,7 +22,10 @@
 // n the scan printed then receives them. --meter: the reception meter (include/sdr_multi_meter.h) beside the
 // receiver, with or without --tune -- PREFIX.meter (per block NCH rows of 64 bytes, sdr_meter_row) and
 // PREFIX.status (per channel the run's mean readings and its STEREO / RDS / OFFTUNE / DEAD_AIR flags);
-// the PCM and the RDS text are those of a run without it. --deemph US (0, 50 or 75) and --blend (needs
+// the PCM and the RDS text are those of a run without it. --rf (needs --meter, not with --fast): the RF
+// readings too (SDR_FLAG_IF_ENVELOPE, sdr_meter_rf) -- PREFIX.rf (per block NCH rows of 32 bytes,
+// sdr_meter_rf_row) and PREFIX.rfstatus (per channel the run's level in dBFS, envelope ripple, C/N, deepest
+// fade and crest, and WEAK); every other file is that of a run without it. --deemph US (0, 50 or 75) and --blend (needs
 // --meter): the audio finishing stage (include/sdr_multi_audio.h) -- PREFIX.audio, in the layout of PREFIX.pcm,
 // holds the audio de-emphasised with US microseconds (75 when only --blend is given) and, with --blend,
 // blended to mono where the meter finds no pilot; every other file is that of a run without them.
@@ -79,12 +82,14 @@
 namespace {
 [[noreturn]] void usage() {
     std::fprintf(stderr, "usage: sdr_multi NCH [--mode 0-3] [--in FILE|-] [--out PREFIX] [--fast] [--cus N] "
-                         "[--tune FILE] [--meter] [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L] [--rds-carrier ref|quad]]\n"
+                         "[--tune FILE] [--meter [--rf]] [--deemph US] [--blend] [--demod ref|phase] [--rds-decode [--rds-correct N] [--rds-clock ref|track] [--rds-soft L] [--rds-carrier ref|quad]]\n"
                          "       sdr_multi NROWS --scan [--mode 0-3] [--in FILE|-] [--out PREFIX] [--scan-blocks B] "
                          "[--step K] [--thr DB]\n"
                          "       sdr_multi NCH --wide W [--shift S] --tune FILE ...   |   sdr_multi NWIDE --wide W [--shift S] --scan ...\n"
                          "  --tune FILE: NCH lines \"src khz\"; the input holds max(src)+1 capture rows per block\n"
                          "  --meter: also write PREFIX.meter (64-byte readings per channel and block) and PREFIX.status\n"
+                         "  --rf: also write PREFIX.rf (32-byte RF readings per channel and block) and PREFIX.rfstatus (level in\n"
+                         "            dBFS, envelope ripple, C/N, fade, crest per channel); needs --meter, not with --fast\n"
                          "  --deemph US: also write PREFIX.audio, the PCM de-emphasised with 0, 50 or 75 microseconds\n"
                          "  --blend: PREFIX.audio blended to mono where the meter finds no pilot (needs --meter)\n"
                          "  --demod phase: the phase discriminator (fm_demod in radians, no fold above if_Fs/4 of deviation;\n"
@@ -165,6 +170,7 @@ int main(int argc, char** argv) {
             wide_gain_set = true;
         }
         else if (a == "--meter") meter = true;
+        else if (a == "--rf") o.flags |= SDR_FLAG_IF_ENVELOPE;
         else if (a == "--blend") blend = finish = true;
         else if (a == "--deemph" && i + 1 < argc) {
             const std::string us = argv[++i];
@@ -214,6 +220,7 @@ int main(int argc, char** argv) {
     o.in_path = in.c_str();
     o.out_prefix = out.c_str();
     if (blend && !meter) usage();
+    if ((o.flags & SDR_FLAG_IF_ENVELOPE) && (!meter || (o.flags & SDR_FLAG_FAST_FRONTEND))) usage();   // the meter reads the row
     if ((rds_correct || rds_clock_set) && !rds_decode) usage();
     if (rds_soft && (!rds_decode || rds_clock != SDR_MULTI_RDS_CLOCK_TRACK)) usage();   // only the tracker has reliabilities
     if (rds_quad && (!rds_decode || rds_clock != SDR_MULTI_RDS_CLOCK_TRACK)) usage();   // the tracker reads the rotated rows

@@ -20,6 +20,9 @@
 // and sdr_meter_rds after the RDS thread's rds_post, each on its own context and post stream, both on
 // one shared meter; each thread copies the rows out behind its call and hands its part of block b to
 // MeterOut, which joins the two parts, writes PREFIX.meter and keeps the run's sums for PREFIX.status.
+// With SDR_FLAG_IF_ENVELOPE in the options a metered run is RF-metered too: the RF thread's context alone
+// gets the flag, and behind each block's front end, on the same stream, the RF thread calls sdr_meter_rf on
+// the shared meter and copies the RF rows out (RfOut: PREFIX.rf, and the run-long rows of PREFIX.rfstatus).
 // A finished run (include/sdr_multi_audio.h) adds, behind them on the audio thread's post stream,
 // sdr_audio_blend_from_meter (with --blend) and sdr_audio_finish from the block's L/R rows into rows of
 // its own, copied out behind the L/R copy and written to PREFIX.audio.
@@ -120,6 +123,8 @@ bool validate(const RunSpec& r) {
     if (!o || (r.blend && (!r.meter || !r.audio))) return false;
     if ((o->flags & SDR_FLAG_FAST_FRONTEND) && (o->flags & SDR_FLAG_PHASE_DEMOD)) return false;   // sdr_ctx_create's rule
     if (o->flags & SDR_FLAG_RDS_QUAD) return false;   // the engine sets it itself, on the RDS thread's context (carrier)
+    // an RF-metered run: the meter reads the row, and only the exact front ends write it (sdr_ctx_create's rule)
+    if ((o->flags & SDR_FLAG_IF_ENVELOPE) && (!r.meter || (o->flags & SDR_FLAG_FAST_FRONTEND))) return false;
     if (r.audio && sdr_audio_opts_check(o->mode, r.audio) != SDR_OK) return false;
     if (o->nch <= 0 || (!o->in_path && (!o->d_iq || o->nblocks <= 0))) return false;
     if (const sdr_multi_rds* d = r.rds) {   // the decoder's record, and a mode with an RDS bit clock
@@ -565,6 +570,86 @@ struct MeterOut {
     }
 };
 
+// An RF-metered run's host side (SDR_FLAG_IF_ENVELOPE, include/sdr_multi_meter.h). Only the RF thread uses it:
+// behind block b's front end it enqueues sdr_meter_rf and the copy of the RF rows into ring slot b % NR, and
+// handles a slot's rows (PREFIX.rf, the run-long sums) when the ring comes round to it, or at the end.
+void wait_event(hipEvent_t e);           // (below, with the streams' helpers)
+struct RfOut {
+    static constexpr int NR = 8;
+    sdr_meter* m = nullptr;              // the run's meter (MeterOut's)
+    int nch = 0, mode = 0;
+    Pinned<uint8_t> h_rows[NR];          // nch RF rows per slot
+    Event copied[NR];
+    File f;                              // PREFIX.rf
+    long long handled = 0;               // blocks whose rows are written
+    struct Sum {                         // the run-long row (include/sdr_amd.h, sdr_meter_rf_status)
+        double s = 0.0, q = 0.0;
+        long long n = 0;
+        float mn = HUGE_VALF, mx = 0.0f;
+        int flags = 0;
+    };
+    std::vector<Sum> sum;
+    RfOut(const sdr_multi_opts& o, sdr_meter* meter, bool cache) : m(meter), nch(o.nch), mode(o.mode), sum((size_t)o.nch) {
+        for (int i = 0; i < NR; i++) {
+            h_rows[i].take((size_t)nch * sizeof(sdr_meter_rf_row), cache);
+            copied[i].make();
+        }
+        if (o.out_prefix) f.open(std::string(o.out_prefix) + ".rf", "wb");
+    }
+    void handle(long long upto) {
+        for (; handled < upto; handled++) {
+            const int h = (int)(handled % NR);
+            wait_event(copied[h]);
+            const sdr_meter_rf_row* rows = reinterpret_cast<const sdr_meter_rf_row*>(h_rows[h].p);
+            for (int c = 0; c < nch; c++) {
+                const sdr_meter_rf_row& r = rows[c];
+                if (!(r.flags & SDR_METER_ROW_RF)) continue;
+                Sum& a = sum[(size_t)c];
+                a.s += (double)r.env_sum;
+                a.q += (double)r.env_sq;
+                a.n += r.n;
+                a.mn = std::min(a.mn, r.env_min);
+                a.mx = std::max(a.mx, r.env_max);
+                a.flags |= r.flags;
+            }
+            if (f && std::fwrite(rows, sizeof(sdr_meter_rf_row), (size_t)nch, f) != (size_t)nch) die("cannot write the .rf file");
+        }
+    }
+    // block b's front end is enqueued on s
+    void block(long long b, sdr_ctx* ctx, hipStream_t s) {
+        handle(b - NR + 1);              // the slot this block reuses
+        check_sdr(sdr_meter_rf(m, ctx, s), "sdr_meter_rf");
+        const sdr_meter_rf_row* d_rows = nullptr;
+        check_sdr(sdr_meter_rf_rows(m, &d_rows), "sdr_meter_rf_rows");
+        const int h = (int)(b % NR);
+        check_hip(hipMemcpyAsync(h_rows[h].p, d_rows, (size_t)nch * sizeof(sdr_meter_rf_row), hipMemcpyDeviceToHost, s),
+                  "hipMemcpyAsync");
+        check_hip(hipEventRecord(copied[h], s), "hipEventRecord");
+    }
+    // PREFIX.rfstatus: per channel the run-long row's readings under the default options
+    void write_status(const std::string& path) const {
+        File t;
+        t.open(path, "w");
+        sdr_meter_rf_opts ro{};
+        sdr_meter_rf_opts_default(&ro);
+        for (int c = 0; c < nch; c++) {
+            Sum a = sum[(size_t)c];
+            while (a.n > INT32_MAX) {    // (the row's n is an int32: halve the three sums, the means stay)
+                a.s *= 0.5;
+                a.q *= 0.5;
+                a.n /= 2;
+            }
+            sdr_meter_rf_row r{};
+            if (a.flags) r = sdr_meter_rf_row{(float)a.s, (float)a.q, a.mn, a.mx, (int32_t)a.n, a.flags, {0, 0}};
+            sdr_meter_rf_state st{};
+            check_sdr(sdr_meter_rf_status(mode, &r, &ro, &st), "sdr_meter_rf_status");
+            std::fprintf(t, "ch %d: level_dbfs %.3f ripple %.3f cnr_db %.3f fade_db %.3f crest_db %.3f flags %s\n", c,
+                         st.level_dbfs, st.ripple, st.cnr_db, st.fade_db, st.crest_db,
+                         (st.flags & SDR_METER_RF_WEAK) ? "WEAK" : "-");
+        }
+    }
+};
+
 // A finished run's audio side: the stage, its device rows (two, as d_lr) and pinned copies (as h_lr)
 struct AudioFin {
     sdr_audio* a = nullptr;
@@ -639,6 +724,7 @@ struct Shared : NoCopy {
     std::optional<AudioRes> ar;
     std::optional<RdsRes> rr;
     std::optional<MeterOut> meter;       // a metered run
+    std::optional<RfOut> rf;             // an RF-metered run (the RF thread's)
     std::optional<AudioFin> fin;         // a finished run
     ThreadSafeQueue<FmBatch*> q;
     std::deque<Batch> batches;
@@ -785,6 +871,7 @@ void rf_thread(Shared* sh) {
             check_hip(hipEventRecord(rows_done[k], sf), "hipEventRecord");
         } else if (sh->tuned) check_sdr(sdr_frontend_tuned(ctx, src, stride, sf), "sdr_frontend_tuned");
         else check_sdr(sdr_frontend(ctx, src, stride, sf), "sdr_frontend");
+        if (sh->rf) sh->rf->block(b, ctx, sf);
         if (!dev_in) check_hip(hipEventRecord(fe_done[(int)(b & 1)], sf), "hipEventRecord");
         FmBatch* fb = sh->q.acquire();
         for (auto& e : fb->released) check_hip(hipStreamWaitEvent(sf, e, 0), "hipStreamWaitEvent");
@@ -797,6 +884,7 @@ void rf_thread(Shared* sh) {
     }
     sh->q.push(nullptr);                                    // end of stream
     check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");   // before this thread's buffers go
+    if (sh->rf) sh->rf->handle(sh->blocks);
     if (!dev_in) {
         harvest(sh->blocks, true);
         sh->read_s = rd->read_s;
@@ -1098,9 +1186,12 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     sh.tuned = spec.tune != nullptr;
     sh.rows = spec.wide ? spec.wide->nwide : spec.tune ? spec.tune->nsrc : spec.o->nch;
     const sdr_multi_opts& o = sh.o;
-    // (the RDS thread's context alone runs the quadrature branch, and only in a run that derotates)
+    // (the RDS thread's context alone runs the quadrature branch, and only in a run that derotates; the RF thread's
+    // alone has a front end, and with it the IF envelope row of an RF-metered run)
     for (int i = 0; i < 3; i++)
-        sh.ctx[i].take(o.device, o.nch, o.mode, i == 2, o.flags | (i == 2 && spec.carrier ? SDR_FLAG_RDS_QUAD : 0), sw.ctx_cache);
+        sh.ctx[i].take(o.device, o.nch, o.mode, i == 2,
+                       (i == 0 ? o.flags : o.flags & ~SDR_FLAG_IF_ENVELOPE) | (i == 2 && spec.carrier ? SDR_FLAG_RDS_QUAD : 0),
+                       sw.ctx_cache);
     mark("contexts");
     // pooled contexts keep their tuning over sdr_ctx_reset: set it on every context of a tuned run,
     // clear it on those of an untuned one
@@ -1151,6 +1242,7 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     sh.rr.emplace(o, spec.rds, spec.rds_clock == SDR_MULTI_RDS_CLOCK_TRACK ? spec.track : nullptr, spec.soft, spec.carrier,
                   sh.info.n_rds, sw.pin_cache);
     if (spec.meter) sh.meter.emplace(o, *spec.meter, sw.pin_cache);
+    if (sh.meter && (o.flags & SDR_FLAG_IF_ENVELOPE)) sh.rf.emplace(o, sh.meter->m, sw.pin_cache);
     if (spec.audio) sh.fin.emplace(o, *spec.audio, spec.blend, lr_bytes, sw.pin_cache);
     mark("consumer buffers");
     // two recycled device batches (threadsafequeue.h's one slot, plus the one the producer fills meanwhile)
@@ -1201,6 +1293,7 @@ void run(const RunSpec& spec, const Switches& sw, const Trace& mark, sdr_multi_s
     check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize");
     if (sh.split) check_split(*sh.split, sh.split->report(spec.wide->clips, spec.fmt, nullptr));
     if (sh.meter && o.out_prefix) sh.meter->write_status(std::string(o.out_prefix) + ".status");
+    if (sh.rf && o.out_prefix) sh.rf->write_status(std::string(o.out_prefix) + ".rfstatus");
 }
 
 int multi_run(const RunSpec& spec, sdr_multi_stats* stats) {
