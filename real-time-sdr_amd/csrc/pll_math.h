@@ -197,6 +197,32 @@ PLLM_HD Phase phase_detect(float eI, float eQ, double c, double s, double mr, in
 // ------------------------------------------------------------------------------------------
 constexpr double MAGIC = 6755399441055744.0;   // 1.5 * 2^52: fma(x, c, MAGIC) - MAGIC = rint(x c)
 constexpr double EPS_ABS_E2 = 0x1p-46;
+// The cut at +-pi (k_pll's fast chunk tests no |e| range; rounds 1-14 required |RN32(e)| < pi - 2^-30
+// per step). atan2 is cut along the negative real axis, and e = base + d is a point of [-pi, pi] only
+// if base and the reference's atan2 lie on the same side of that cut. They do, by the step's algebra:
+//  * what the algebra needs: fI0 = RN32(c), fQ0 = RN32(s) of the carried f64 c = cos r, s = sin r,
+//    with b = [r < 0] and the quadrant carried beside them (pll_load, or the previous fast step: a tie
+//    that fails its proof changes no part of this), and a valid rx, |x| >= 2^-60. A start state that
+//    is not of this form carries mr = NaN, an invalid rx is a NaN, and either reaches both state words
+//    of the pair through e: the state range at the chunk's end rejects them, as it does an infinite e.
+//  * |d| = |Y rx| <= |c s| (|p - q| + 2^-51) <= 2^-22 |sin r| (above). With |m| <= 1, |base| <=
+//    3 pi / 4 and e is nowhere near the cut. With |m| = 2, base_angle_n takes m = 2 for r >= 0 and
+//    m = -2 for r < 0: base = +-(pi - |r|), so |d| < |r| keeps base + d on base's side, at a distance
+//    |r| (1 - 2^-22) from the cut that EPS_ABS_E2 bounds like any other e.
+//  * the reference's side is the sign of its eQ, zeros included (atan2(+-0, eI < 0) = +-pi). With
+//    |m| = 2 the rotation by i^q leaves eQ = +-eQ0 = -+RN32(x fQ0), and RN32 keeps the sign of an
+//    exact product even when it underflows to a subnormal or to zero, fQ0 that of s, s that of r:
+//    the sign of eQ is the sign base_angle_n reads from r and x (quadrant by quadrant in DESIGN.md
+//    4c). r = 0 only for t = 0 (t is an f32, q pi/2 is not one for q != 0; the reduction's error,
+//    2^-77, is far below the smallest |r|, ~2^-30 for q != 0): then s = fQ0 = +0, b = 0, m = 2 for
+//    x < 0, and the reference's eQ = x * -(+0) = +0 gives +pi as well.
+//  * underflow can move d by 2^-150 |rx| <= 2^-90, more than a subnormal |r|; but then base + d is
+//    within 2^-90 of +-pi on either side, and every double within 3.2e-8 of +-pi rounds to the f32
+//    +-0x40490FDB that the reference's +-RN64(pi) rounds to: only the sign matters, and the sign is
+//    base's (|base| <= 2 PIO2 < pi, so the fma's rounding cannot flip it).
+// tools/pllmath/validate_step2.cpp runs the chunk's proofs without the range test on t next to every
+// k pi / 2, |k| <= 8, with inputs of both signs: every chunk the range test alone would have
+// rejected has the reference's bits ("e_range_only_wrong": 0).
 
 PLLM_HD double pll_rx(float x) {
     const float ax = __builtin_fabs(x);

@@ -74,8 +74,9 @@ __device__ __forceinline__ PllRegs pll_load(const sdr_pll_state& st, double w) {
 }
 
 // Per-chunk proof obligations of the fast path (VGPR accumulators, one check per chunk):
-//   * every phase-detector result is at least EPS_ABS_E2 from an f32 rounding boundary (split)
-//     and |e| < pi - 2^-30 (so the wrap to [-pi, pi] is the reference's),
+//   * every phase-detector result is at least EPS_ABS_E2 from an f32 rounding boundary (split);
+//     there is no test of |e|: base_angle_n puts e on the reference's side of the cut at +-pi
+//     whenever the other proofs hold (pll_math.h, "The cut at +-pi"),
 //   * every cos/sin is at least 64 f64 ulps from an f32 tie (tie),
 //   * the chunk ends with |phaseEst| < 2^28, |integrator| < 2^20 (finite: a NaN or inf from an
 //     invalid input -- pll_rx gives NaN for |x| < 2^-60 -- propagates into both),
@@ -83,7 +84,6 @@ __device__ __forceinline__ PllRegs pll_load(const sdr_pll_state& st, double w) {
 //     table (TAB) the launch checked |w| (|toff| + n + 1) < 1.375 * 2^29, which leaves room for
 //     |phaseEst| < 2^28 plus 16 steps of drift; without it the chunk's largest |t| is tracked.
 struct PllProof {
-    float emaxf = 0.0f;     // max |RN32(ed)| (PLL_EMAX_F)
     uint32_t split = 0u;
     uint32_t tie = ~0u;
     float tmax = 0.0f;
@@ -91,11 +91,9 @@ struct PllProof {
 // (the A/B variants of this step measured and dropped -- e bracket order, bracket by fma, pre-loop
 // wait, packed loop filter, first table entries carried, one lane per chain, no trigArg table -- are
 // recorded in profiles/HISTORY.md)
-// |e| bound of the fast phase detector (the wrap to [-pi, pi] is the reference's below it)
+// |e| bound of the checked step's phase detector (beyond it the step calls the reference's atan2; the
+// fast chunk needs no such bound, pll_math.h "The cut at +-pi")
 constexpr double PLL_EMAX = pllm::PI - 0x1p-30;
-// the largest f32 below PLL_EMAX: RN32 is monotone, so |RN32(ed)| < PLL_EMAX_F implies |ed| < PLL_EMAX_F
-constexpr float PLL_EMAX_F = __builtin_bit_cast(float, 0x40490FDAu);
-static_assert((double)PLL_EMAX_F < PLL_EMAX, "PLL_EMAX_F");
 constexpr double PLL_TAB_WT_MAX = 0x1.6p29;   // |w * trigOffset| bound of the table path (above)
 
 #ifndef SDR_PLL_COUNT
@@ -103,8 +101,9 @@ constexpr double PLL_TAB_WT_MAX = 0x1.6p29;   // |w * trigOffset| bound of the t
 #endif
 #if SDR_PLL_COUNT
 // [lane-chunks, lane-chunks that failed their proof, wave-chunks, wave-chunks redone]
-// [4..7]: lane-chunks failing the e range, the e bracket, the cos/sin ties, the state range (a chunk
-// can fail several); [8], [9]: failed lane-chunks of job 0 (stereo 19 kHz) and job 1 (RDS 114 kHz)
+// [4..7]: lane-chunks failing the e range (no longer a proof of the fast chunk: always 0), the e
+// bracket, the cos/sin ties, the state range (a chunk can fail several); [8], [9]: failed lane-chunks
+// of job 0 (stereo 19 kHz) and job 1 (RDS 114 kHz)
 constexpr int PLL_NCOUNTS = 10;
 __device__ unsigned long long g_pll_counts[PLL_NCOUNTS];
 __device__ __forceinline__ void pll_count_reasons(bool emax_bad, bool split_bad, bool tie_bad, bool state_bad) {
@@ -355,11 +354,12 @@ __device__ __forceinline__ void pll_step_split(SplitRegs& r, float xs, double rx
     const double base = pllm::base_angle_n(pllm::lo_word(rx), r.nq1, r.b, r.mr);
     // (ed = base + rx qA + rx qB, own product first, is one dependent level shorter but needs both
     // bracket ends per lane: 2 instructions more, slower, profiles/r03/ab_pll_split.txt; again on
-    // the lane-specialised loop filter: 205.3 -> 219.0 cycles per step, profiles/r07/ab_pll_pair_lf.txt)
+    // the lane-specialised loop filter: 205.3 -> 219.0 cycles per step, profiles/r07/ab_pll_pair_lf.txt;
+    // and with one bracket end on a timing-only build with 2 VALU of proofs removed: 193.7 -> 197.1,
+    // profiles/r15/pll_step2/ab_ceilings.txt: the step is bound by what it issues, not by this chain)
     const double Y = q + pair_swap(q);
     const double ed = pllm::fma_(Y, rx, base);
     const float e = (float)ed;                                     // = RN32(atan2) when proven
-    pf.emaxf = fmaxf(pf.emaxf, __builtin_fabsf(e));               // f32: two steps per v_max3_f32
     // pll.cpp:41-42, one state word per lane: the two products and the two first sums are the same
     // two opcodes, so each lane issues them once for its own word,
     //   s1 = s + RN(K e)        A: RN(phaseEst + Kp e)    B: RN(integrator + Ki e) = integrator'
@@ -400,7 +400,8 @@ __device__ __forceinline__ void pll_step_split(SplitRegs& r, float xs, double rx
     // Estrin and than a two-level form (profiles/r03/ab_pll_split3.txt)
     // (Estrin, two dependent levels shorter for two multiplies more, measured again in round 5:
     // 212 -> 224 cycles per step, with or without s_setprio; profiles/r05/ab_pll_est.txt; and in
-    // round 7 on the lane-specialised loop filter: 205.3 -> 216.2, profiles/r07/ab_pll_pair_lf.txt)
+    // round 7 on the lane-specialised loop filter: 205.3 -> 216.2, profiles/r07/ab_pll_pair_lf.txt; in
+    // round 15 with issue slots freed first: 193.7 -> 210.5, a two-level form 206.2, profiles/r15/pll_step2/)
     double P = pllm::fma_(z, L.c5, L.c4);
     P = pllm::fma_(z, P, L.c3);
     P = pllm::fma_(z, P, L.c2);
@@ -500,14 +501,13 @@ __device__ __forceinline__ void pair_chunk(PairChain& p, const float (&xb)[PLL_C
                      "+v"(wv[14]), "+v"(wv[15]));
         pll_step_split<TAB>(p.r, xb[j], rb[j], p.w, TAB ? wv[j] : 0.0, tv[j], pf, L);
     }
-    // this lane's proof: its half of the e bracket, the e range, its own rounding ties, and
-    // the state range (a NaN from an invalid input fails it)
-    const bool ok = (pf.emaxf < PLL_EMAX_F) & (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) &
-                    (__builtin_fabs(p.r.s) < L.smax) & (TAB || (pf.tmax < 0x1p30f));
+    // this lane's proof: its half of the e bracket, its own rounding ties, and the state range (a NaN
+    // or an infinity from an invalid input, from an invalid start state or from e fails it)
+    const bool ok = (pf.split == 0u) & (pf.tie > pllm::TIE_MIN) & (__builtin_fabs(p.r.s) < L.smax) &
+                    (TAB || (pf.tmax < 0x1p30f));
 #if SDR_PLL_COUNT
     pll_count_chunk(ok);
-    pll_count_reasons(!(pf.emaxf < PLL_EMAX_F), pf.split != 0u, !(pf.tie > pllm::TIE_MIN),
-                      !(__builtin_fabs(p.r.s) < L.smax));
+    pll_count_reasons(false, pf.split != 0u, !(pf.tie > pllm::TIE_MIN), !(__builtin_fabs(p.r.s) < L.smax));
 #endif
     // the partner's verdict, read with every lane of the pair active (under `ok && ...` the
     // exchange would sit in a branch, and a lane reading a disabled partner keeps its own value)
