@@ -43,7 +43,11 @@ extern "C" {
 #define SDR_NBITS_POISONED (-2)           /* nbits[ch] of sdr_rds_bits; rds_clean rows are NaN */
 
 /* Context flags */
-#define SDR_FLAG_FAST_FRONTEND 0x1  /* FMA front end: fm_demod within 1e-6 rel., not bit-exact */
+#define SDR_FLAG_FAST_FRONTEND 0x1  /* int8 MFMA front end, not bit-exact: every fm_demod sample within the derived
+                                     * bound tol() of tests/fast_fe_model.py of the f64 definition (I/Q within
+                                     * 2^-(F+1) sum|x| + 3 * 2^-24 |y|; tests/test_gpu_fast_frontend.py), and
+                                     * within 1e-5 of the reference normwise per block (the north star;
+                                     * tests/test_gpu_pipeline.py) */
 #define SDR_FLAG_PLL_LIBM 0x2       /* PLL via per-step f64 libm calls (A/B reference) */
 #define SDR_FLAG_KEEP_INTERMEDIATES 0x4  /* post stages store every intermediate row (carrier, stereo_dc,
                                           * ipll) for sdr_ctx_buffer; by default the NCO, mixers and

@@ -113,8 +113,8 @@ __global__ __launch_bounds__(BLK) void k_frontend(
 // converted once and feeds up to R outputs. Conversion: u8 -> signed byte (u ^ 0x80 = u - 128)
 // -> f32 m via SDWA sext; with taps pre-scaled by 2^-7 (hs = h/128, exact) the product
 // fl(hs*m) equals the reference's fl(h*x), x = (u-128)/128, bit for bit.
-//   exact: v_pk_mul_f32 + v_pk_add_f32 (separate roundings, like filter.cpp:115)
-//   FAST:  v_pk_fma_f32 (one rounding per tap; fm_demod within ~1e-6 relative)
+//   v_pk_mul_f32 + v_pk_add_f32 (separate roundings, like filter.cpp:115); fast mode is not a
+//   variant of this kernel but k_frontend_mfma below, with its own error bound
 // A tile computes TILE = 256*R outputs starting one before the first fm_demod sample it writes
 // (the discriminator's carry, demod.cpp:16), so tiles advance by TILE-1. The u8 window is staged
 // in LDS with coalesced dword loads (D even) or u16 loads (D odd).
@@ -175,12 +175,25 @@ __device__ __forceinline__ f32x2 fe_add_v(f32x2 a, f32x2 b) {
 // channel. Block b's outputs need a 256-sample window w_b (x[D*c_b - 100 + s], s < 256, of which
 // 15*D + 101 are used) and y[c_b + i] = sum_s W[i][s] * w_b[s] with the Toeplitz tap matrix
 // W[i][s] = h[D*i + 100 - s]. Samples are exact int8 (u8 - 128); the taps are fixed point with
-// 2^-(31 - ceil(log2 max|h|)) resolution split into FT_ND = 4 balanced base-256 digits, so
-// v_mfma_i32_16x16x64_i8 (rows = 16 outputs, columns = 8 blocks x {I, Q}, K = 4 x 64) accumulates
-// each digit plane exactly in int32 and the planes combine exactly in f64: y is the correctly
-// rounded f32 of the convolution with the quantised taps (<= ~1e-8 absolute from the exact one,
-// so ~1e-6 relative even at 1-LSB input amplitude; 3 digits measured 1e-4 on a filter start-up
-// transient). North-star tolerance 1e-5 relative on fm_demod, RDS bits bit-exact: tested.
+// 2^-F = 2^-(30 - ceil(log2 max|h|)) resolution split into FT_ND = 4 balanced base-256 digits, so
+// v_mfma_i32_16x16x64_i8 (rows = 16 outputs, columns = 16 blocks, I and Q as two groups, K = 4 x 64)
+// accumulates each digit plane P_0..P_3 exactly in int32 (|P| <= 128 * 128 * 101 < 2^21). The planes
+// pair up exactly in int32, hI = (P_0 << 8) + P_1 and lI = (P_2 << 8) + P_3 (|.| < 2^30), and then
+// y = fmaf((float)hI, ys * 65536, (float)lI * ys) in f32, ys = 2^-(F+7): two int -> f32 conversions
+// and one fma. Both conversions can round: |lI| passes 2^24 on ordinary input, |hI| at full scale
+// where F = 33 (2.4e7 at 2.4 MS/s; 1.4e7 < 2^24 where F = 32). y is not the correctly rounded
+// convolution. Against the f64 convolution c with the f32 taps, per component, with u = 2^-24 and
+// X1 = sum of |x| = |u8 - 128| / 128 over the 101 samples the taps meet:
+//   |y - c| <= e = 2^-(F+1) X1                              the taps' fixed-point rounding
+//                + 3u (1 + 2^-22) (|c| + 2^-(F+1) X1        the conversions, the products, the fma
+//                                  + 514 * 2^(7-F) X1)
+// (F = 33 at 2.4 MS/s: 5.8e-11 X1 + 1.8e-7 |c|, at most 5.9e-9 + 1.8e-7 |c|). fm_demod then lies
+// within the per-sample bound tol() of tests/fast_fe_model.py of the f64 definition (its docstring
+// derives it from the lines of ft_tile_iq): tests/test_gpu_fast_frontend.py on every synth kind,
+// full-scale and silent rows, every decimation, both stagings; tests/test_fast_fe_model.py shows
+// that a dropped digit plane, a wrong tap digit, a wrong carry row or a wrong prev_in exceeds it.
+// North star 1e-5 normwise per block against the f32 reference, RDS bits bit-exact:
+// tests/test_gpu_pipeline.py. (3 digits measured 1e-4 on a filter start-up transient.)
 // Staging: u8 I/Q pairs -> planar int8 I and Q rows in LDS (v_perm deinterleave); each B
 // fragment is then one ds_read_b128 (16 consecutive samples of one component).
 // ------------------------------------------------------------------------------------------
